@@ -11,6 +11,13 @@ keypoint lists are all-gathered over RCCL (xGMI) each step: weak scaling.
 Prints ONE JSON line (rank 0).  Workload defaults to BASELINE.json's metric
 configuration: 3840x2160 (4K), 4 octaves x 5 scales.
 
+A plain run sets up, warms up, times --steps steps, writes the last timed
+step's keypoints with --dump-outputs DIR, and prints the line.  Everything
+else this file measures or checks takes runs of its own and is behind --full:
+`sustained`, the isolated per-stage passes behind `roofline`, `verified` (the
+last timed keypoint list against a synchronous detection on a fresh context)
+and the CPU baselines; without --full those fields are null.
+
 `roofline` is SURVEY.md §8d's north-star quantity, the whole Gaussian+DoG
 pass (one k_gauss_dog launch per octave): B_alg = 4WH + sum_o 4 P_o (S+3) +
 sum_o 4 P_o (S+2) (the input read, every Gaussian and DoG plane written in
@@ -166,6 +173,38 @@ def cpu_baseline_js(img_full, O, S, sample_w, sample_h):
                       % (sample_w, sample_h, O, S, d["node"], d["seconds"], d["keypoints"])}
 
 
+DUMP_CAP_BYTES = 48 << 20  # --dump-outputs: keypoints.npy stays under this (the whole dump under 64 MB)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(path, kp, counts=None):
+    """--dump-outputs: what a caller of the timed path receives after its last
+    step, as float64 .npy files (int32 and fp64 fields are exact in float64).
+    keypoints.npy: one row per keypoint record, columns in KEYPOINT_DTYPE's
+    field order; a list larger than DUMP_CAP_BYTES is cut to a fixed seeded
+    choice of rows (in list order), their indices in keypoint_rows.npy.
+    counts.npy: [all keypoints, rows written] and, for single-GPU detections,
+    the library's counts of the last detection."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = int(kp.shape[0])
+    names = kp.dtype.names
+    cap = DUMP_CAP_BYTES // (8 * len(names))
+    rows = np.arange(n)
+    if n > cap:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+        kp = kp[rows]
+    arr = np.empty((kp.shape[0], len(names)), dtype=np.float64)
+    for j, f in enumerate(names):
+        arr[:, j] = kp[f]
+    np.save(os.path.join(path, "keypoints.npy"), arr)
+    np.save(os.path.join(path, "keypoint_rows.npy"), rows.astype(np.float64))
+    c = [n, arr.shape[0]]
+    if counts is not None:
+        c += [counts[k] for k in ("candidates", "low_contrast", "keypoints", "singular", "exact")]
+    np.save(os.path.join(path, "counts.npy"), np.array(c, dtype=np.float64))
+
+
 def host_cores():
     """CPU threads this process may use (the GPU box's share is 16)."""
     try:
@@ -215,10 +254,18 @@ def main():
                          "detect_sharded_device: band octaves, all-gathered next-octave base, tail octaves one per "
                          "rank, block-major merge); strong scaling.  Defaults to 7680x4320, 6 octaves x 5 scales "
                          "unless --width/--height/--octaves are given")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what takes runs of its own: `sustained`, the isolated "
+                         "passes behind `roofline`, `verified` and the CPU baselines (null in a plain run)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write rank 0's keypoint list of the last timed step (what a "
+                         "caller of the timed path receives) to DIR/keypoints.npy, keypoint_rows.npy and "
+                         "counts.npy, float64; the inputs are seeded, so two builds run with the same arguments "
+                         "compare output for output")
     ap.add_argument("--sustain-s", type=float, default=5.0,
-                    help="seconds of the same pipelined loop after the timed region, reported as `sustained` "
-                         "(0 = skip)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="with --full: seconds of the same pipelined loop after the timed region, reported as "
+                         "`sustained` (0 = skip)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--pmc", default=None,
                     help="PMC summary (tools/pmc_launches.py) for roofline.traffic; default: the committed "
                          "profiles/*pmc*.json of the latest round tag for this configuration")
@@ -226,6 +273,8 @@ def main():
     ap.add_argument("--cpu-sample-js", default="1920x1080",
                     help="crop WxH timed on the single-threaded JS restatement (the C port's crop; about 15 s on the GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     big = args.shard_image
     args.width = args.width or (7680 if big else 3840)
     args.height = args.height or (4320 if big else 2160)
@@ -385,15 +434,19 @@ def main():
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
     # What the timed region computed: the keypoint records of its last image
-    # (the pipelined own-stream schedule), checked after the measurements
-    # against a synchronous detection of the same input on a fresh context.
-    kp_timed = ctxs[(NI - 1) % nin].keypoints().tobytes()
+    # (the pipelined own-stream schedule), written out by --dump-outputs and,
+    # with --full, checked after the measurements against a synchronous
+    # detection of the same input on a fresh context.
+    counts = ctxs[(NI - 1) % nin].counts()
+    kp_last = ctxs[(NI - 1) % nin].keypoints() if args.full or args.dump_outputs else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, kp_last, counts)
     # Steady state: the same pipelined loop for a few seconds (thousands of
     # images; no per-image host work beyond the settle), its own clock.
     # The image count comes from the timed region's max-over-ranks time, so
     # every rank runs the same number of per-image collectives.
     sustained = None
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize(dev)
@@ -425,7 +478,7 @@ def main():
     iso = {"gauss_dog_ms": 0.0, "gauss_oct0_ms": 0.0, "extrema_ms": 0.0, "refine_ms": 0.0}
     iso_oct = [0.0] * O
     n_iso = 10
-    for _ in range(n_iso):
+    for _ in range(n_iso if args.full else 0):
         if batched:
             ctx.detect_batch_device_async(d_imgs.data_ptr(), Bt, W, H, params)
         else:
@@ -436,26 +489,28 @@ def main():
             iso[k] += t[k] / n_iso
         for o, v in enumerate(ctx.octave_timings()):
             iso_oct[o] += v / n_iso
-    pass_kernels = ctx.pass_kernels()  # the library's own record of the launches (sift_last_pass_kernels)
-    with sift_amd.Context(dev) as vctx:
-        if batched:  # the batch against the same images detected one by one
-            ref = []
-            for b in range(Bt):
-                vctx.detect_device(d_imgs[b].data_ptr(), W, H, params)
-                ref.append(vctx.keypoints().tobytes())
-            verified = b"".join(ref) == kp_timed
-        else:
-            vctx.detect_device(d_img.data_ptr(), W, H, params)
-            verified = vctx.keypoints().tobytes() == kp_timed
-    if not verified:
-        print("bench.py: rank %d: the timed region's last keypoint list differs from a synchronous detection"
-              % rank, file=sys.stderr)
+    verified = None
+    if args.full:
+        kp_timed = kp_last.tobytes()
+        with sift_amd.Context(dev) as vctx:
+            if batched:  # the batch against the same images detected one by one
+                ref = []
+                for b in range(Bt):
+                    vctx.detect_device(d_imgs[b].data_ptr(), W, H, params)
+                    ref.append(vctx.keypoints().tobytes())
+                verified = b"".join(ref) == kp_timed
+            else:
+                vctx.detect_device(d_img.data_ptr(), W, H, params)
+                verified = vctx.keypoints().tobytes() == kp_timed
+        if not verified:
+            print("bench.py: rank %d: the timed region's last keypoint list differs from a synchronous detection"
+                  % rank, file=sys.stderr)
     K = args.steps
     ms_per_step = elapsed / K * 1e3
     value = world * Bt * W * H / (elapsed / K) / 1e6
-    counts = ctxs[(NI - 1) % nin].counts()
 
     if rank == 0:
+        pass_kernels = ctx.pass_kernels()  # the library's own record of the launches (sift_last_pass_kernels)
         gauss_ms = stage["gauss_dog_ms"] / NI
         oct0_ms = stage["gauss_oct0_ms"] / NI
         ipd = Bt if batched else 1  # the pass of one detection covers ipd images
@@ -575,7 +630,10 @@ def main():
             "cpu_baseline_all_cores": None,
             "cpu_baseline_js": None,
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if not args.full:  # its isolated passes did not run
+            out["roofline"] = out["verified_what"] = None
+        out["full"] = args.full
+        if args.full and world == 1 and not args.no_cpu_baseline:
             sw, sh = (int(v) for v in args.cpu_sample.split("x"))
             out["cpu_baseline"] = cpu_baseline(img, O, S, min(sw, W), min(sh, H))
             nt = host_cores()
@@ -623,6 +681,9 @@ def bench_shard_image(args, dist, world, rank, dev):
         e = torch.tensor([elapsed], dtype=torch.float64, device="cuda:%d" % dev)
         dist.all_reduce(e, op=dist.ReduceOp.MAX)
         elapsed = float(e.item())
+    if args.dump_outputs and rank == 0:  # the merged whole-image list of the last timed step
+        import numpy as np
+        dump_outputs(args.dump_outputs, np.frombuffer(out.cpu().numpy().tobytes(), dtype=sift_amd.KEYPOINT_DTYPE))
     K = args.steps
     if rank == 0:
         out = {

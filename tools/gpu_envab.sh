@@ -10,7 +10,7 @@ for r in $(seq $reps); do
   for e in "$@"; do
     i=$((i+1))
     [ "$e" = "-" ] && e=""
-    env $e timeout -k 10 200 python $R/bench.py --steps 200 --warmup 10 --no-cpu-baseline > $O/envab_$i.json 2> $O/envab_$i.err || { echo "setting '$e' failed"; tail -5 $O/envab_$i.err; exit 1; }
+    env $e timeout -k 10 200 python $R/bench.py --full --steps 200 --warmup 10 --no-cpu-baseline > $O/envab_$i.json 2> $O/envab_$i.err || { echo "setting '$e' failed"; tail -5 $O/envab_$i.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/envab_$i.json')); print('[$e]', d['value'], d['ms_per_step'], d['roofline']['launch_ms'])"
   done
 done

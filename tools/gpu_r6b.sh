@@ -12,7 +12,7 @@ for rep in 1 2; do
   i=0
   for e in "SIFT_RWP=0" "SIFT_RWP=1 SIFT_RWP_BIG=0" "SIFT_RWP=1 SIFT_RWP_BIG=1"; do
     i=$((i+1))
-    env SIFT_HIP_LIB=$R/build_ab/${VAR:-exp2}.so $e timeout -k 10 200 python bench.py --steps 200 --warmup 10 --no-cpu-baseline > $O/r6b_$i.json 2> $O/r6b_$i.err || { echo "bench '$e' failed"; tail -5 $O/r6b_$i.err; exit 1; }
+    env SIFT_HIP_LIB=$R/build_ab/${VAR:-exp2}.so $e timeout -k 10 200 python bench.py --full --steps 200 --warmup 10 --no-cpu-baseline > $O/r6b_$i.json 2> $O/r6b_$i.err || { echo "bench '$e' failed"; tail -5 $O/r6b_$i.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/r6b_$i.json')); r=d['roofline']; print('[$e]', d['value'], d['ms_per_step'], r['launch_ms'], r['frac'], [o['iso_ms'] for o in r['per_octave']], 'x', r['extrema_stage']['iso_ms'], 'ref', r['refine_stage']['iso_ms'], d['verified'])"
   done
 done

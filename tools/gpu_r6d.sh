@@ -9,5 +9,5 @@ cat $O/r6d_tcc.txt
 i=0
 for C in "TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum GRBM_GUI_ACTIVE" "TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_128B_sum GRBM_GUI_ACTIVE" "FETCH_SIZE GRBM_GUI_ACTIVE"; do
   i=$((i+1))
-  timeout -s KILL 60 rocprofv3 --pmc $C --output-format csv -d $O/stall_r6d_$i -o run -- python3 $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --sustain-s 0 --overlap none --inflight 1 > /dev/null 2> $O/stall_r6d_$i.err && echo "pass $i ok" || { echo "pass $i failed"; tail -3 $O/stall_r6d_$i.err; }
+  timeout -s KILL 60 rocprofv3 --pmc $C --output-format csv -d $O/stall_r6d_$i -o run -- python3 $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --sustain-s 0 --overlap none --inflight 1 > /dev/null 2> $O/stall_r6d_$i.err && echo "pass $i ok" || { echo "pass $i failed"; tail -3 $O/stall_r6d_$i.err; }
 done
