@@ -212,10 +212,6 @@ struct sift_ctx {
   DBuf ambbitmap;                              // ambiguous words (k_exact_words)
   bool x_words = false;                        // this extrema stage lists ambiguous words, not keys
   DBuf cand_key, cand_val, cand_keep;          // ordered candidates
-  DBuf patch, wslot, cand_patch;               // first-step patches captured by the scan (ExtremaLaunch.patch)
-  DBuf pre;                                    // the scan's first refinement steps (ExtremaLaunch.pre, SIFT_XREFINE)
-  bool x_patch = false;                        // this extrema stage captures patches
-  bool has_patch = false;                      // cand_patch indexes the current slots
   DBuf lowbitmap, lowrowcount, lowrowoff;      // low-contrast list (SIFT_F_LOW_CONTRAST_LIST)
   DBuf low_key, low_val, late_key, late_val;
   DBuf keep, pos;                              // keypoint compaction
@@ -426,7 +422,7 @@ int sift_ctx_destroy(sift_ctx* ctx) {
                   &ctx->temp, &ctx->rgba, &ctx->alpha, &ctx->display, &ctx->mm_parts, &ctx->merge_tab,
                   &ctx->lowbitmap, &ctx->lowrowcount, &ctx->lowrowoff, &ctx->low_key, &ctx->low_val,
                   &ctx->late_key, &ctx->late_val, &ctx->band_cnt, &ctx->band_first, &ctx->band_start,
-                  &ctx->perm, &ctx->patch, &ctx->wslot, &ctx->cand_patch, &ctx->pre, &ctx->kp_soa, &ctx->keep_tile};
+                  &ctx->perm, &ctx->kp_soa, &ctx->keep_tile};
   for (DBuf* b : bufs) b->release();
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
@@ -470,7 +466,6 @@ static int setup_geometry(sift_ctx* ctx, int W, int H, const sift_params* p, con
   ctx->p = *p;
   ctx->scan_first = 0;
   ctx->planes_first = 0;
-  ctx->has_patch = false;
   ctx->P.vsum = nullptr;
   ctx->P.vsum_oct = -1;
   ctx->W = W;
@@ -1074,29 +1069,6 @@ static int extrema_prepare(sift_ctx* ctx, hipStream_t st, int nf) {
   }
   L.lowbitmap = ctx->want_low ? ctx->lowbitmap.as<unsigned long long>() : nullptr;
   L.lowrowcount = ctx->want_low ? ctx->lowrowcount.as<unsigned>() : nullptr;
-  // Patch capture (SIFT_PATCH=0: the refinement gathers every step, experiments).
-  static const int capture = exp_knob("SIFT_PATCH", 1);
-  const size_t slots = (size_t)ni * extrema_units(P) * kPatchUnitSlots;
-  // the scan's patch stores take 32-bit byte offsets (a larger batch gathers);
-  // the in-scan first step (SIFT_XREFINE) runs the fast pass's fp32 bounds,
-  // so not on caller-supplied (exact) planes
-  ctx->x_patch = kXCapture && capture != 0 &&
-                 (SIFT_XREFINE == 1 ? !exact_planes : slots * kPatchFloats * sizeof(float) < ((size_t)1 << 31));
-  ctx->has_patch = false;
-  if (ctx->x_patch) {
-    if (SIFT_XREFINE == 1) {
-      HIPCHK(ctx->pre.ensure(std::max<size_t>(slots, 1) * sizeof(Keypoint)));
-      L.pre = ctx->pre.as<Keypoint>();
-      L.min_blur = ctx->p.min_blur;
-      L.min_interpixel_distance = ctx->p.min_interpixel_distance;
-    } else {
-      HIPCHK(ctx->patch.ensure(std::max<size_t>(slots, 1) * kPatchFloats * sizeof(float)));
-      L.patch = ctx->patch.as<float>();
-    }
-    HIPCHK(ctx->wslot.ensure((size_t)words * sizeof(unsigned)));
-    HIPCHK(ctx->cand_patch.ensure((size_t)ctx->cand_cap * sizeof(unsigned)));
-    L.wslot = ctx->wslot.as<unsigned>();
-  }
   return SIFT_OK;
 }
 
@@ -1139,14 +1111,10 @@ static int extrema_finish(sift_ctx* ctx) {
     E.keep = ctx->cand_keep.as<unsigned>();
     E.cap = ctx->cand_cap;
     // Deferred values (SIFT_DEFER_VALUES=0: gathered here, experiments): the
-    // refinement reads each candidate's plane value from its own patch.
+    // refinement reads each candidate's plane value from the DoG plane, with
+    // the 3x3x3 neighbourhood it gathers there anyway.
     static const int defer = exp_knob("SIFT_DEFER_VALUES", 1);
     E.deferred = defer != 0;
-    if (ctx->x_patch) {  // the scanned octaves carry captured patches, the fused ones gather
-      E.wslot = ctx->wslot.as<unsigned>();
-      E.cand_patch = ctx->cand_patch.as<unsigned>();
-      for (int o = ctx->x_nf; o < P.O; ++o) E.patch_oct |= 1u << o;
-    }
     HIPCHK(launch_emit(P, E, ctx->stream));
   }
   if (ctx->want_low) {  // the certain low-contrast extrema, in order (same scan + emission as the candidates)
@@ -1226,7 +1194,6 @@ static int extrema_finish(sift_ctx* ctx) {
   ctx->slot_cap = (int)ctx->cand_cap;
   ctx->has_keep = true;
   ctx->slots_rows = true;
-  ctx->has_patch = ctx->x_patch;
   ctx->ext_pending = true;
   return SIFT_OK;
 }
@@ -1321,11 +1288,6 @@ static int refine_enqueue(sift_ctx* ctx) {
     R.uncertain = ctx->uncertain.as<unsigned>();
     R.counters = cnt;
     R.perm = nullptr;
-    if (ctx->has_patch && ctx->slots_rows) {
-      R.cand_patch = ctx->cand_patch.as<unsigned>();
-      if (SIFT_XREFINE == 1) R.pre = ctx->pre.as<Keypoint>();
-      else R.patch = ctx->patch.as<float>();
-    }
     static const int band_order = exp_knob("SIFT_BAND_ORDER", 1);
     if (band_order && ctx->slots_rows) {
       BandOrder B{};
@@ -1365,29 +1327,12 @@ static int refine_enqueue(sift_ctx* ctx) {
     HIPCHK(launch_refine_fast(P, R, ctx->stream));
     HIPCHK(hipEventRecord(ctx->ev_heavy, ctx->stream));  // the rest is latency-bound tail work
     // Uncertain decisions exist only with fp32-rounded native planes.
-#ifndef SIFT_WIDE_EXACT
-#define SIFT_WIDE_EXACT 0  // 1: 256-thread exact refinement for whole images too (A/B builds)
-#endif
-    R.wide_exact = SIFT_WIDE_EXACT || ctx->o_first > 0;  // a tail piece (sift_detect_from_seed*): latency over throughput
+    R.wide_exact = ctx->o_first > 0;  // a tail piece (sift_detect_from_seed*): latency over throughput
     if (ctx->dog_source == kNative) HIPCHK(launch_refine_exact(P, R, ctx->stream));
-#if SIFT_KEEP_SCAN
     HIPCHK(ctx->keep_tile.ensure(keep_tiles(cap) * sizeof(unsigned)));
     HIPCHK(launch_keep_compact(P, R.status, R.cand_key, ctx->keep.as<unsigned>(), ctx->pos.as<unsigned>(),
                                ctx->keep_tile.as<unsigned>(), R.n, cap, ctx->own_lo, ctx->own_hi, cnt + kBlk, R.kp,
                                ctx->kp.as<Keypoint>(), ctx->stream));
-#else
-    HIPCHK(launch_status_to_keep(P, R.status, R.cand_key, ctx->keep.as<unsigned>(), R.n, cap, ctx->own_lo,
-                                 ctx->own_hi, cnt + kBlk, ctx->stream));
-    size_t tb = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ctx->keep.as<unsigned>(), ctx->pos.as<unsigned>(), cap,
-                                            ctx->stream));
-    HIPCHK(ctx->temp.ensure(tb));
-    tb = ctx->temp.bytes;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->temp.p, tb, ctx->keep.as<unsigned>(), ctx->pos.as<unsigned>(), cap,
-                                            ctx->stream));
-    HIPCHK(launch_scatter_keypoints(ctx->keep.as<unsigned>(), ctx->pos.as<unsigned>(), R.kp, R.n, cap,
-                                    ctx->kp.as<Keypoint>(), ctx->stream));
-#endif
     HIPCHK(launch_count_keypoints(P, ctx->pos.as<unsigned>(), ctx->keep.as<unsigned>(), R.cand_key, R.n, cap,
                                   cnt + kCntKp, cnt + kBlk, ctx->stream));
     if (ctx->p.flags & SIFT_F_KEYPOINT_ORIGINS) {
@@ -1582,7 +1527,6 @@ int sift_set_candidates(sift_ctx* ctx, const sift_extremum* cand, size_t n) {
   ctx->ext_pending = false;
   ctx->has_keep = false;
   ctx->slots_rows = false;
-  ctx->has_patch = false;
   ctx->have_cand = true;
   return SIFT_OK;
 }

@@ -28,11 +28,14 @@
 #include "sift_exact.h"
 #include "sift_kernels.h"
 #include "sift_xmask.h"
-#include "sift_refine.h"
 
 #ifndef SIFT_XLOAD_AUX
 #define SIFT_XLOAD_AUX 0  // cache-policy bits of the scan's DoG loads (gfx950: 1 sc0, 2 nt, 16 sc1)
 #endif
+
+// No FP contraction in this file (as in sift_refine.h): the exact fp64
+// decisions write out every fma they mean, nothing else may fuse.
+#pragma clang fp contract(off)
 
 namespace sift {
 
@@ -52,141 +55,20 @@ struct XUnit {
   unsigned long long* lowbitmap;  // the same for the certain low-contrast extrema (LOWL)
   unsigned* lowrowcount;
   unsigned low;
-  unsigned pbase, pcount;  // patch capture: the unit's first slot, slots taken
-  __amdgpu_buffer_rsrc_t prsrc;  // the patch buffer (< 4 GiB: extrema_prepare checks)
-  float* cap;          // SIFT_XREFINE: this wave's capture slots in LDS
-  unsigned capa;       // ... their LDS byte address
-  bool capture;        // patches are captured (L.patch or L.pre)
   long long word0;     // index of (s_first, row 0, word 0) in L.bitmap (ambiguous word list)
   long long boff;      // lane l < NP-2: l h nw + xw (scale s_first + l, row 0, this word)
   long long roff;      // lane l < NP-2: l h (scale s_first + l, row 0)
 };
 
-// SIFT_XGLDS: the rows stream through a per-wave LDS ring of kXRing rows
-// (buffer_load_dword ... lds: no VGPR holds a row in flight), kXRing rows
-// ahead instead of the three the register window affords.
-#ifndef SIFT_XGLDS
-#define SIFT_XGLDS 0
-#endif
-#ifndef SIFT_XRING
-#define SIFT_XRING 5
-#endif
-constexpr int kXRing = SIFT_XRING;
-[[maybe_unused]] constexpr int kXRingFloats = kXRing * (kXMaxGroup + 2) * 64;  // one wave's ring
-
-template <int NP>
-struct XRing {
-  unsigned lds;     // LDS byte address of the wave's ring (wave-uniform)
-  unsigned vaddr;   // ... + lane * 4
-  int islot, cslot; // next slot to fill / to read
-  int next, last;   // next row to issue; rows past `last` re-read it
-};
-
-// Issues row ring.next (clamped) into slot islot: NP loads, one per plane.
-template <int NP>
-__device__ __forceinline__ void x_issue(const XUnit<NP>& U, XRing<NP>& R) {
-  const unsigned rofs = (unsigned)min(R.next, R.last) * (unsigned)U.w * 4u;
-  const unsigned base = R.lds + (unsigned)(R.islot * NP * 256);
-#pragma unroll
-  for (int q = 0; q < NP; ++q)
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(U.rsrc, (__attribute__((address_space(3))) void*)(size_t)(base + q * 256), 4,
-                                             (int)U.xoff, (int)(rofs + (unsigned)q * U.plane_bytes), 0,
-                                             SIFT_XLOAD_AUX);
-  R.islot = R.islot + 1 == kXRing ? 0 : R.islot + 1;
-  ++R.next;
-}
-
-// The oldest row in flight (kXRing rows are: wait until kXRing - 1 remain),
-// read from its slot; its slot then takes the next row.
-template <int NP>
-__device__ __forceinline__ void x_take(const XUnit<NP>& U, XRing<NP>& R, float (&dst)[NP]) {
-  constexpr int N = NP * (kXRing - 1);  // loads younger than the row (stores in between only make this wait longer)
-  static_assert(N <= 63, "vmcnt");
-  __builtin_amdgcn_s_waitcnt((N & 15) | ((N >> 4) << 14) | (7 << 4) | (15 << 8));
-  const unsigned a = R.vaddr + (unsigned)(R.cslot * NP * 256);
-#pragma unroll
-  for (int q = 0; q < NP; ++q) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(dst[q]) : "v"(a), "i"(q * 256));
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  R.cslot = R.cslot + 1 == kXRing ? 0 : R.cslot + 1;
-  x_issue(U, R);
-}
-
 template <int NP>
 __device__ __forceinline__ void x_load(const XUnit<NP>& U, float (&dst)[NP], int row) {
   // buffer loads: lane byte offset in a VGPR, row + plane offset in an SGPR
   const unsigned rofs = (unsigned)row * (unsigned)U.w * 4u;
-#if defined(SIFT_X_PROBE2COL)  // timing probe: 8-byte loads, two columns per lane (half the waves)
-#pragma unroll
-  for (int q = 0; q < NP; ++q) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(
-        U.rsrc, (int)U.xoff, (int)(rofs + (unsigned)q * U.plane_bytes), SIFT_XLOAD_AUX);
-    dst[q] = __builtin_bit_cast(float, v[0]) + __builtin_bit_cast(float, v[1]);
-  }
-  return;
-#endif
 #pragma unroll
   for (int q = 0; q < NP; ++q)
     dst[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                            U.rsrc, (int)U.xoff, (int)(rofs + (unsigned)q * U.plane_bytes),
                                            SIFT_XLOAD_AUX));
-}
-
-// Patch capture of scale q at centre row y (ExtremaLaunch.patch): each
-// candidate's 19 first-step values come from three lanes -- its own column (9
-// values) and the columns left and right of it (5 each) -- all already in the
-// window, so no DPP moves.  The word's candidates take the next slots of the
-// unit (a wave-uniform count: no atomics -- one global counter serialised
-// ~600 K atomics at the L2, 0.42 -> 6.8 ms).  Returns the slot of the first
-// one (~0u: the unit is out of slots, these candidates gather in the refinement).
-// SIFT_XREFINE: the same fields go to the wave's LDS slots (U.cap, local slot
-// numbers), field 19 = the candidate's key relative to U.key_base.
-template <int NP, int A, int B, int C>
-__device__ __forceinline__ unsigned x_capture(const XWin<NP>& Wn, XUnit<NP>& U, const ExtremaLaunch& L,
-                                              const int Q, unsigned long long b, unsigned rel_key) {
-  const unsigned cnt = (unsigned)__popcll(b);
-  if (U.pcount + cnt > (unsigned)kPatchUnitSlots) return ~0u;
-  const unsigned base = U.pbase + U.pcount;
-#if SIFT_XREFINE
-  // ds_write_b32 one value at a time (inline asm): left to itself the compiler
-  // merges the fields into b64 / b96 / b128 stores, whose consecutive source
-  // registers cost copies and ~20 VGPRs across the scan (a wave per SIMD).
-  const unsigned sa = U.capa + U.pcount * (unsigned)(kPatchFloats * 4);
-  U.pcount += cnt;
-  constexpr int kStride = kPatchFloats * 4;
-#define X_ST(v, vo, field) \
-  asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(sa + (unsigned)(vo)), "v"(v), "i"(4 * (field)))
-#else
-  U.pcount += cnt;
-  // Buffer stores of the window registers themselves: the slot's byte offset
-  // in one VGPR, the word's first slot in an SGPR, the field in the
-  // instruction's offset (16-byte or flat stores would copy each quad into
-  // consecutive registers / keep 64-bit addresses: a wave per SIMD less).
-  const int sb = (int)(base * (unsigned)(kPatchFloats * 4));
-  constexpr int kStride = kPatchFloats * 4;
-#define X_ST(v, voff, field) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(v), U.prsrc, (voff) + 4 * (field), sb, 0)
-#endif
-  const int lane = U.lane;
-  if ((b >> lane) & 1ull) {  // the candidate's own column: d(k, a, 1)
-    const int vo = (int)lane_prefix(b) * kStride;
-    X_ST(Wn.cv[A][Q - 1], vo, 0); X_ST(Wn.cv[B][Q - 1], vo, 1); X_ST(Wn.cv[C][Q - 1], vo, 2);
-    X_ST(Wn.cv[A][Q], vo, 3); X_ST(Wn.cv[B][Q], vo, 4); X_ST(Wn.cv[C][Q], vo, 5);
-    X_ST(Wn.cv[A][Q + 1], vo, 6); X_ST(Wn.cv[B][Q + 1], vo, 7); X_ST(Wn.cv[C][Q + 1], vo, 16);
-#if SIFT_XREFINE
-    X_ST(__uint_as_float(rel_key), vo, 19);
-#endif
-  }
-  if (lane < 63 && ((b >> (lane + 1)) & 1ull)) {  // left of a candidate: d(1, a, 0), d(0, 1, 0), d(2, 1, 0)
-    const int vo = (int)lane_prefix(b >> 1) * kStride;
-    X_ST(Wn.cv[A][Q], vo, 8); X_ST(Wn.cv[B][Q], vo, 9); X_ST(Wn.cv[C][Q], vo, 10);
-    X_ST(Wn.cv[B][Q - 1], vo, 11); X_ST(Wn.cv[B][Q + 1], vo, 17);
-  }
-  if (lane > 0 && ((b >> (lane - 1)) & 1ull)) {  // right of a candidate: d(1, a, 2), d(0, 1, 2), d(2, 1, 2)
-    const int vo = (int)lane_prefix(b << 1) * kStride;
-    X_ST(Wn.cv[A][Q], vo, 12); X_ST(Wn.cv[B][Q], vo, 13); X_ST(Wn.cv[C][Q], vo, 14);
-    X_ST(Wn.cv[B][Q - 1], vo, 15); X_ST(Wn.cv[B][Q + 1], vo, 18);
-  }
-  return base;
-#undef X_ST
 }
 
 // v_writelane_b32 (no clang builtin here): lane LANE of dst = the uniform v.
@@ -207,15 +89,6 @@ __device__ __forceinline__ void x_for(F&& f) {
 // Centre row y (slots A = y-1, B = y, C = y+1): decide every scale of the group.
 template <int NP, int A, int B, int C, bool LOWL>
 __device__ __forceinline__ void x_centre(const XWin<NP>& Wn, XUnit<NP>& U, const ExtremaLaunch& L, int y) {
-#if defined(SIFT_X_PROBE)  // timing probe: no decisions
-  {
-    float acc = 0.f;
-#pragma unroll
-    for (int q = 0; q < NP; ++q) acc += Wn.hx[B][q] + Wn.hn[A][q];
-    if (acc == 1234.5f) U.low += 1;
-    return;
-  }
-#endif
   float vx[NP], vn[NP];
 #pragma unroll
   for (int q = 0; q < NP; ++q) {
@@ -230,7 +103,6 @@ __device__ __forceinline__ void x_centre(const XWin<NP>& Wn, XUnit<NP>& U, const
   // 0..NP-3 is written each row; the other lanes' contents are never used.
   unsigned wlo = __builtin_nondeterministic_value(0u), whi = __builtin_nondeterministic_value(0u);
   unsigned llo = __builtin_nondeterministic_value(0u), lhi = __builtin_nondeterministic_value(0u);  // LOWL
-  unsigned wsl = ~0u;                   // lane q-1: patch slot of scale q's first candidate
   x_for<1, NP - 2>([&](auto qc) {
     constexpr int q = decltype(qc)::value;
     const float v = Wn.cv[B][q];
@@ -254,26 +126,17 @@ __device__ __forceinline__ void x_centre(const XWin<NP>& Wn, XUnit<NP>& U, const
     const unsigned long long word = bit >> 1;  // lanes 1..62 -> bits 0..61
     x_writelane<q - 1>(wlo, (unsigned)word);
     x_writelane<q - 1>(whi, (unsigned)(word >> 32));
-    if (kXCapture && U.capture && bit) {
-      const unsigned ps = x_capture<NP, A, B, C>(Wn, U, L, q, bit, key - U.key_base);
-      if (U.lane == q - 1) wsl = ps;
-    }
     if (LOWL) {
       const unsigned long long lw = lowmask >> 1;
       x_writelane<q - 1>(llo, (unsigned)lw);
       x_writelane<q - 1>(lhi, (unsigned)(lw >> 32));
     }
   });
-#if defined(SIFT_X_PROBE3)  // timing probe: decisions without bitmap stores
-  if (wlo == 0x12345u && whi == 0x777u) U.low += 1;
-  return;
-#endif
   if (U.lane < NP - 2) {
     // lane l stores scale s_first + l's word of row y: a uniform row pointer
     // plus the lane's (scale, word) offset
     const unsigned long long* const brow = U.bitmap + (long long)y * U.nw;
     const_cast<unsigned long long*>(brow)[U.boff] = ((unsigned long long)whi << 32) | wlo;
-    if (kXCapture && U.capture && (wlo | whi)) L.wslot[U.word0 + ((long long)U.lane * U.h + y) * U.nw + U.xw] = wsl;
     const unsigned wcnt = (unsigned)(__popc(wlo) + __popc(whi));
     if (wcnt) atomicAdd(&U.rowcount[U.roff + y], wcnt);
     if (LOWL) {
@@ -284,68 +147,9 @@ __device__ __forceinline__ void x_centre(const XWin<NP>& Wn, XUnit<NP>& U, const
   }
 }
 
-#if SIFT_XREFINE
-// The first refinement step of every candidate the unit captured (lane j takes
-// slots j, j + 64, ...): refine_step on the fp32 planes with the fast pass's
-// error bounds, exactly as k_refine_fast's first iteration from a captured
-// patch; the outcome goes to pre[slot] (kPre* codes).
-template <int NP>
-__device__ __forceinline__ void x_first_steps(const Pyramid& P, const ExtremaLaunch& L, const XUnit<NP>& U) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the capture's ds_write_b32s (inline asm) have landed
-  const int o = U.o;
-  const unsigned plane = (unsigned)U.plane, w = (unsigned)U.w;
-  const int moff = (P.row0 * 2) >> o;
-  for (unsigned j = (unsigned)U.lane; j < U.pcount; j += 64) {
-    const float* pp = U.cap + j * kPatchFloats;
-    const float4 c0 = *reinterpret_cast<const float4*>(pp), c1 = *reinterpret_cast<const float4*>(pp + 4);
-    const float4 lf = *reinterpret_cast<const float4*>(pp + 8), rt = *reinterpret_cast<const float4*>(pp + 12);
-    const float4 ex = *reinterpret_cast<const float4*>(pp + 16);
-    const unsigned rel = __float_as_uint(ex.w);
-    const unsigned sq = rel / plane, rem = rel - sq * plane, mr = rem / w;
-    const int s = U.s_first + (int)sq, m = (int)mr, n = (int)(rem - mr * w);
-    const float v19[19] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, ex.x,
-                           lf.x, lf.y, lf.z, lf.w, ex.y, rt.x, rt.y, rt.z, rt.w, ex.z};
-    constexpr int at[19] = {1, 4, 7, 10, 13, 16, 19, 22, 25, 9, 12, 15, 3, 21, 11, 14, 17, 5, 23};
-    double d[27];
-    double mx = 0;
-#pragma unroll
-    for (int k = 0; k < 27; ++k) d[k] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 19; ++k) {
-      d[at[k]] = (double)v19[k];
-      mx = fmax(mx, fabs((double)v19[k]));
-    }
-    const double value = (double)c1.x;  // d(1, 1, 1)
-    const double dval = fabs(value) * 0x1p-24;
-    const double delta = mx * (0x1p-24 + 0x1p-40);
-    const StepOut R = refine_step<true>(d, o, s, m, n, value, delta, dval, P.S, P.ND, U.h, U.w, P.thr, false,
-                                        L.min_blur / L.min_interpixel_distance);
-    Keypoint k;
-    k.octave = kPreDefer;
-    if (!R.uncertain) {
-      if (R.state == 3) k.octave = kPreSingular;
-      else if (R.state == 2) k.octave = kPreDiscard;
-      else if (R.state == 1) {
-        if (!R.imprecise) {
-          make_keypoint(k, o, R, P.S, L.min_blur, L.min_interpixel_distance, moff);
-          k.octave = kPreKeep;
-        }
-      } else {
-        k.octave = kPreMoved;
-        k.scale_level = R.s;
-        k.local_y = R.m;
-        k.local_x = R.n;
-        k.interp_value = value;
-      }
-    }
-    L.pre[U.pbase + j] = k;
-  }
-}
-#endif
-
 template <int NP, bool LOWL>
-__device__ __forceinline__ void x_scan(const Pyramid& P, const ExtremaLaunch& L, int b, int u, int o, int s_first,
-                                       int xw, int y0, int y1, float* cap, float* ring) {
+__device__ __forceinline__ void x_scan(const Pyramid& P, const ExtremaLaunch& L, int b, int o, int s_first,
+                                       int xw, int y0, int y1) {
   const Octave& oc = P.oct[o];
   XUnit<NP> U;
   U.plane = (long long)oc.h * oc.w;
@@ -359,10 +163,6 @@ __device__ __forceinline__ void x_scan(const Pyramid& P, const ExtremaLaunch& L,
   U.o = o;
   const int x = xw * kXW - 1 + U.lane;
   U.xoff = 4u * (unsigned)clampi(x, 0, oc.w - 1);
-#if defined(SIFT_X_PROBE2COL)
-  if (xw & 1) return;
-  U.xoff = 4u * (unsigned)clampi(2 * kXW * (xw >> 1) - 2 + 2 * U.lane, 0, oc.w - 2);
-#endif
   U.plane_bytes = (unsigned)(4 * U.plane);
   U.colmask = __ballot(U.lane >= 1 && U.lane <= kXW && x >= 1 && x <= oc.w - 2);
   U.base = P.dog + b * P.dog_bstride + oc.dog_off + (long long)(s_first - 1) * U.plane;
@@ -380,47 +180,7 @@ __device__ __forceinline__ void x_scan(const Pyramid& P, const ExtremaLaunch& L,
     U.lowrowcount = L.lowrowcount + rb;
   }
   U.low = 0;
-  U.pbase = (unsigned)(b * L.units_per_img + u) * (unsigned)kPatchUnitSlots;
-  U.pcount = 0;
-  U.capture = L.pre != nullptr || L.patch != nullptr;
-  if (SIFT_XPATCH && L.patch) U.prsrc = __builtin_amdgcn_make_buffer_rsrc(L.patch, 0, -1, 0x00020000);
-
-  U.cap = cap;
-  U.capa = (unsigned)(size_t)(__attribute__((address_space(3))) float*)cap;
   XWin<NP> Wn;
-#if SIFT_XGLDS
-  XRing<NP> R;
-  R.lds = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) float*)ring);
-  R.vaddr = R.lds + 4u * (unsigned)U.lane;
-  R.islot = R.cslot = 0;
-  R.next = y0 - 1;
-  R.last = y1 + 1;
-#pragma unroll
-  for (int k = 0; k < kXRing; ++k) x_issue(U, R);
-  {
-    float t[NP];
-    x_take(U, R, t);
-    x_derive<NP, 2>(Wn, t);
-    x_take(U, R, t);
-    x_derive<NP, 0>(Wn, t);
-  }
-  for (int y = y0; y <= y1; y += 3) {
-    float t[NP];
-    x_take(U, R, t);
-    x_derive<NP, 1>(Wn, t);
-    x_centre<NP, 2, 0, 1, LOWL>(Wn, U, L, y);
-    if (y + 1 > y1) break;
-    x_take(U, R, t);
-    x_derive<NP, 2>(Wn, t);
-    x_centre<NP, 0, 1, 2, LOWL>(Wn, U, L, y + 1);
-    if (y + 2 > y1) break;
-    x_take(U, R, t);
-    x_derive<NP, 0>(Wn, t);
-    x_centre<NP, 1, 2, 0, LOWL>(Wn, U, L, y + 2);
-  }
-  // the ring's last loads land in LDS: drained before the wave's LDS can be reallocated
-  __builtin_amdgcn_s_waitcnt((7 << 4) | (15 << 8));
-#else
   {
     float r_m1[NP], r_0[NP];
     x_load(U, r_m1, y0 - 1);
@@ -446,19 +206,6 @@ __device__ __forceinline__ void x_scan(const Pyramid& P, const ExtremaLaunch& L,
     x_load(U, Wn.raw[0], min(y + 6, y1 + 1));
     x_centre<NP, 1, 2, 0, LOWL>(Wn, U, L, y + 2);
   }
-#endif
-#if SIFT_XREFINE
-  if (U.capture && U.pcount) {
-    if constexpr (SIFT_XREFINE == 1) {
-      x_first_steps<NP>(P, L, U);
-    } else {  // SIFT_XREFINE=2: the LDS slots copied out whole (16-byte stores, contiguous per unit)
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      const float4* src = reinterpret_cast<const float4*>(U.cap);
-      float4* dst = reinterpret_cast<float4*>(L.patch + (size_t)U.pbase * kPatchFloats);
-      for (unsigned t = (unsigned)U.lane; t < U.pcount * (kPatchFloats / 4); t += 64) dst[t] = src[t];
-    }
-  }
-#endif
   if (U.lane == 0 && U.low) atomicAdd(&L.counters[1], U.low);
 }
 
@@ -499,24 +246,12 @@ __global__ __launch_bounds__(256, SIFT_XMINW) void k_extrema(const Pyramid P, co
   const int per = P.S / L.ng, rem = P.S % L.ng;
   const int s_first = 1 + g * per + min(g, rem);
   const int cnt = per + (g < rem ? 1 : 0);
-#if SIFT_XREFINE
-  __shared__ __attribute__((aligned(16))) float xcap[4][kPatchUnitSlots * kPatchFloats];
-  float* const cap = xcap[threadIdx.x >> 6];
-#else
-  float* const cap = nullptr;
-#endif
-#if SIFT_XGLDS
-  __shared__ __attribute__((aligned(16))) float xring[4][kXRingFloats];
-  float* const ring = xring[threadIdx.x >> 6];
-#else
-  float* const ring = nullptr;
-#endif
   switch (cnt) {
-    case 1: x_scan<3, LOWL>(P, L, b, u, o, s_first, xw, y0, y1, cap, ring); break;
-    case 2: x_scan<4, LOWL>(P, L, b, u, o, s_first, xw, y0, y1, cap, ring); break;
-    case 3: x_scan<5, LOWL>(P, L, b, u, o, s_first, xw, y0, y1, cap, ring); break;
-    case 4: x_scan<6, LOWL>(P, L, b, u, o, s_first, xw, y0, y1, cap, ring); break;
-    default: x_scan<7, LOWL>(P, L, b, u, o, s_first, xw, y0, y1, cap, ring); break;
+    case 1: x_scan<3, LOWL>(P, L, b, o, s_first, xw, y0, y1); break;
+    case 2: x_scan<4, LOWL>(P, L, b, o, s_first, xw, y0, y1); break;
+    case 3: x_scan<5, LOWL>(P, L, b, o, s_first, xw, y0, y1); break;
+    case 4: x_scan<6, LOWL>(P, L, b, o, s_first, xw, y0, y1); break;
+    default: x_scan<7, LOWL>(P, L, b, o, s_first, xw, y0, y1); break;
   }
 }
 
@@ -548,11 +283,9 @@ __global__ __launch_bounds__(256) void k_emit(const Pyramid P, const EmitLaunch 
   const int nw = E.nw[o];
   const long long wrow = im * E.words_per_img + E.word_off[o] + (long long)row * nw;
   const unsigned long long* bm = E.bitmap + wrow;
-  const bool patched = E.cand_patch && ((E.patch_oct >> o) & 1u);
   for (int xw0 = 0; xw0 < nw; xw0 += 64) {
     const int xw = xw0 + lane;
     unsigned long long word = xw < nw ? bm[xw] : 0ull;
-    unsigned ps = (patched && word) ? E.wslot[wrow + xw] : ~0u;  // patch slot of the word's first candidate
     unsigned c = (unsigned)__popcll(word);
     // inclusive wave scan of c
     unsigned inc = c;
@@ -571,9 +304,7 @@ __global__ __launch_bounds__(256) void k_emit(const Pyramid P, const EmitLaunch 
         E.keys[pos] = kbase + (unsigned)x;
         E.value[pos] = E.deferred ? __builtin_bit_cast(double, 0x7ff8000000000000ull) : (double)Dc[x];
         if (E.keep) E.keep[pos] = 1u;
-        if (E.cand_patch) E.cand_patch[pos] = ps;
       }
-      if (ps != ~0u) ++ps;
       ++pos;
     }
     base += __shfl(inc, 63);
@@ -805,7 +536,7 @@ hipError_t launch_exact_words(const Pyramid& P, ExactLaunch X, hipStream_t st) {
   return hipGetLastError();
 }
 
-static int extrema_unit_table(const Pyramid& P, int* unit_off, int* nw) {
+static void extrema_unit_table(const Pyramid& P, int* unit_off, int* nw) {
   const int ng = (P.S + kXMaxGroup - 1) / kXMaxGroup;
   int units = 0;
   for (int o = 0; o < P.O; ++o) {
@@ -815,18 +546,12 @@ static int extrema_unit_table(const Pyramid& P, int* unit_off, int* nw) {
     if (oc.h >= 3 && oc.w >= 3 && P.S >= 1) units += ng * nw[o] * ((oc.h - 2 + kXRows - 1) / kXRows);
   }
   unit_off[P.O] = units;
-  return units;
-}
-
-int extrema_units(const Pyramid& P) {
-  int uo[kMaxOctaves + 1], nw[kMaxOctaves];
-  return extrema_unit_table(P, uo, nw);
 }
 
 hipError_t launch_extrema(const Pyramid& P, ExtremaLaunch& L, hipStream_t st, int o_begin, int o_end) {
   L.n_oct = P.O;
   L.ng = (P.S + kXMaxGroup - 1) / kXMaxGroup;
-  L.units_per_img = extrema_unit_table(P, L.unit_off, L.nw);
+  extrema_unit_table(P, L.unit_off, L.nw);
   L.u_begin = L.unit_off[o_begin];
   L.u_end = L.unit_off[o_end];
   if (L.u_end <= L.u_begin) return hipSuccess;

@@ -95,54 +95,8 @@ struct ExtremaLaunch {
   // layout as bitmap) and lists the word's index (into bitmap) in amb_keys
   // (counters[kAmbWords] of them); k_exact_words re-decides a whole word.
   unsigned long long* ambbitmap;
-  // Patch capture (patch != nullptr): for every candidate bit the scan writes
-  // the 19 fp32 DoG values of its first refinement step (kPatchFloats per
-  // candidate) into its unit's kPatchUnitSlots slots -- unit (image b, u) owns
-  // slots [(b * units_per_img + u) * kPatchUnitSlots, ...), taken in scan
-  // order with a wave-uniform counter, no atomics -- and, for each non-zero
-  // bitmap word, the slot of its first candidate to wslot (same index as
-  // bitmap; ~0u: no patch, the unit's slots ran out: those candidates gather).
-  float* patch;
-  unsigned* wslot;
-  int units_per_img;
-  // First refinement step in the scan (pre != nullptr, SIFT_XREFINE builds):
-  // the candidate's 19 values are captured into LDS instead of `patch`, and
-  // after its strip the unit takes the first step of background.js:480-664
-  // for each captured candidate (fp32 planes, the fast pass's error bounds),
-  // writing its outcome to pre[slot] (kPre* in .octave; a kept keypoint's
-  // record, or the position a move leads to with the candidate value in
-  // interp_value).  The fast refinement continues from there.
-  Keypoint* pre;
-  double min_blur, min_interpixel_distance;
 };
-// pre[slot].octave: the first step's outcome (kPreDefer: uncertain or
-// imprecise -- the fast refinement starts over from a gather).
-constexpr int kPreMoved = 0, kPreKeep = 1, kPreDiscard = 2, kPreSingular = 3, kPreDefer = 4;
 constexpr int kAmbWords = 8;     // counters slot: listed ambiguous words
-#ifndef SIFT_PATCH_SLOTS
-#define SIFT_PATCH_SLOTS 96
-#endif
-constexpr int kPatchUnitSlots = SIFT_PATCH_SLOTS;  // patch slots per scan unit (4K octave 0: ~40 candidates on average)
-// Scan units per image (one wave each: octave, strip of kXRows rows, word, scale group).
-int extrema_units(const Pyramid& P);
-// Patch capture is built only into A/B libraries (-DSIFT_XPATCH=1): 4K
-// extrema stage 0.40 -> 0.50 ms (148 instead of 111 VGPRs: 3 waves per SIMD;
-// 19 dword stores per candidate) for a refinement stage 0.33 -> 0.27 ms,
-// pipelined 7.10 -> 6.54 Gpix/s (profiles/r4p_patch_capture_ab.txt).
-#ifndef SIFT_XPATCH
-#define SIFT_XPATCH 0
-#endif
-#ifndef SIFT_XREFINE
-#define SIFT_XREFINE 0
-#endif
-constexpr bool kXCapture = (SIFT_XPATCH != 0) || (SIFT_XREFINE != 0);  // the scan captures first-step patches (global / LDS)
-// Captured patch of a candidate at (s, y, x), d(k, a, c) = D_{s-1+k}(y-1+a, x-1+c):
-//   [0..8]   d(k, a, 1) at 3k + a (centre column, all three scales and rows) -- except d(2, 2, 1) at [16]
-//   [8..11]  d(1, 0, 0), d(1, 1, 0), d(1, 2, 0), d(0, 1, 0)   (left column)
-//   [12..15] d(1, 0, 2), d(1, 1, 2), d(1, 2, 2), d(0, 1, 2)   (right column)
-//   [16..19] d(2, 2, 1), d(2, 1, 0), d(2, 1, 2), unused (LDS capture: the candidate's key - key of (s_first, 0, 0))
-// Five 16-byte pieces: the centre lane writes 2 + 1, each side lane 1 + 1.
-constexpr int kPatchFloats = 20;
 
 // One launch over every octave: global row g (one wave each) = row_off[o] +
 // (s-1) h_o + y.
@@ -161,15 +115,10 @@ struct EmitLaunch {
   double* value;
   unsigned* keep;                // nullptr: not written
   unsigned cap;                  // slots in keys/value/keep (overflow is detected by the host)
-  int deferred;                  // 1: value = NaN ("the fp32 plane value"): the refinement reads it from its
-                                 // patch, launch_fill_values before the list is copied out; no plane gather here
+  int deferred;                  // 1: value = NaN ("the fp32 plane value"): the refinement reads it from the
+                                 // DoG plane (the centre of the 3x3x3 neighbourhood it gathers anyway),
+                                 // launch_fill_values before the list is copied out; no plane gather here
   long long words_per_img;       // batch: bitmap words per image (rows per image = row_off[n_oct])
-  // Patch indices (cand_patch != nullptr): cand_patch[pos] = wslot of the
-  // word + the bit's rank in it for octaves in patch_oct (scanned with patch
-  // capture), ~0u elsewhere.
-  const unsigned* wslot;
-  unsigned* cand_patch;
-  unsigned patch_oct;
   unsigned* n_out;               // != nullptr: *n_out = rowoff[n_index] (the list's length), by thread 0
   long long n_index;
 };
@@ -218,9 +167,6 @@ struct RefineLaunch {
   unsigned* counters; // [3] n uncertain, [4] n singular
   const unsigned* perm; // processing order: thread t refines slot perm[t] (nullptr = slot t)
   int wide_exact;       // k_refine_exact: 256 threads per patch (latency) instead of one wave (throughput)
-  const unsigned* cand_patch;  // per slot: captured first-step patch (ExtremaLaunch.patch), ~0u = gather; nullptr = none
-  const float* patch;
-  const Keypoint* pre;  // != nullptr: cand_patch indexes the scan's first-step outcomes (ExtremaLaunch.pre) instead
 };
 
 // Processing order of the fast refinement (band_order): the slots of the
@@ -302,32 +248,25 @@ hipError_t launch_refine_exact(const Pyramid& P, const RefineLaunch& R, hipStrea
 
 // Order-preserving compaction helpers.
 // Entries i >= *n (device count) of the cap-sized arrays are inactive.
-hipError_t launch_scatter_keypoints(const unsigned* keep, const unsigned* pos, const Keypoint* kp,
-                                    const unsigned* n, int cap, Keypoint* out, hipStream_t st);
-// keep[i] = status[i] is a kept keypoint whose candidate row (whole-image
-// octave rows, P.row0 applied) lies in the input rows [own_lo, own_hi) (own_lo
-// < 0: every row; own_hi < 0: no upper bound).  blk (kBlkWords, zeroed by the
-// caller) receives the first slot of every (octave, scale) block of the
-// candidate list at blk[kBlkStart + b], b = o * S + s - 1 (candidates are in
-// key order, so a block is a slot range), or sets blk[kBlkUnsorted] when the
-// list is not in key order.
+// launch_keep_compact: keep[i] = status[i] is a kept keypoint whose candidate
+// row (whole-image octave rows, P.row0 applied) lies in the input rows
+// [own_lo, own_hi) (own_lo < 0: every row; own_hi < 0: no upper bound).  blk
+// (kBlkWords, zeroed by the caller) receives the first slot of every (octave,
+// scale) block of the candidate list at blk[kBlkStart + b], b = o * S + s - 1
+// (candidates are in key order, so a block is a slot range), or sets
+// blk[kBlkUnsorted] when the list is not in key order.
 constexpr int kBlkN = 1024;  // blk[b]: kept keypoints of block b = (image, octave, scale) (launch_count_keypoints)
 static_assert(kBlkN >= kMaxOctaves * kMaxScales, "one image's blocks");
 constexpr int kBlkStart = kBlkN;                  // blk[kBlkStart + b], b <= O*S: first slot of block b
 constexpr int kBlkUnsorted = kBlkStart + kBlkN + 1;
 constexpr int kBlkWords = kBlkUnsorted + 1;
-hipError_t launch_status_to_keep(const Pyramid& P, const int* status, const unsigned* key, unsigned* keep,
-                                 const unsigned* n, int cap, int own_lo, int own_hi, unsigned* blk, hipStream_t st);
 hipError_t launch_scatter_keys(const unsigned* keep, const unsigned* pos, const unsigned* key, const unsigned* n,
                                int cap, unsigned* out, hipStream_t st);
-// launch_status_to_keep + an exclusive scan of keep into pos +
-// launch_scatter_keypoints, with the work bounded by *n instead of cap: keep
-// and pos are written for the slots of the tiles up to slot min(*n, cap)
-// (what launch_count_keypoints and launch_scatter_keys read); tile holds
+// The keep flags, their exclusive scan into pos and the kept keypoints'
+// copies into out, with the work bounded by *n instead of cap: keep and pos
+// are written for the slots of the tiles up to slot min(*n, cap) (what
+// launch_count_keypoints and launch_scatter_keys read); tile holds
 // keep_tiles(cap) words of scratch.
-#ifndef SIFT_KEEP_SCAN
-#define SIFT_KEEP_SCAN 1  // 0: capacity-sized device scan (the round-4 compaction; A/B builds)
-#endif
 constexpr int kKeepTile = 512;  // two slots per thread: 4K (714 K candidates) 1400 tiles
 inline size_t keep_tiles(int cap) { return cap > 0 ? (size_t)(cap + kKeepTile - 1) / kKeepTile : 0; }
 hipError_t launch_keep_compact(const Pyramid& P, const int* status, const unsigned* key, unsigned* keep,

@@ -1,5 +1,4 @@
-// Refinement step shared by the fast refinement (sift_refine.hip) and the
-// first step taken inside the extrema scan (sift_extrema.hip, SIFT_XREFINE).
+// Refinement step of the fast and the exact refinement (sift_refine.hip).
 // FP contraction is off for every function below and for the code that
 // follows this include: the step rounds exactly as the reference does.
 #pragma once

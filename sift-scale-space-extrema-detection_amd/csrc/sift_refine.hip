@@ -58,61 +58,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
     const int h = oc.h, w = oc.w;
     const long long plane = (long long)h * w;
     const float* __restrict__ D = P.dog + im * P.dog_bstride + oc.dog_off;
-    // the first step's patch as captured by the scan (kPatchFloats layout), if any
-    const unsigned pidx = L.cand_patch ? L.cand_patch[i] : ~0u;
-    // (with SIFT_XREFINE=1 cand_patch indexes L.pre instead: no patch buffer)
-    const bool patched = pidx != ~0u && (SIFT_XREFINE != 1 || L.patch);
-    const float* __restrict__ pp = L.patch + (size_t)(patched ? pidx : 0u) * kPatchFloats;
     double value = L.cand_val[i];
     int status = kRefDiscard;
-    int it0 = 0;
-#if SIFT_XREFINE == 1
-    // The scan's first step (L.pre): taken on the fp32 plane value, so only
-    // for candidates whose value is still deferred (an exact re-decision
-    // writes the fp64 value, and the chain starts over from it).
-    if (!EXACT && L.pre && pidx != ~0u && value != value) {
-      const Keypoint pr = L.pre[pidx];
-      if (pr.octave == kPreKeep) {
-        Keypoint k = pr;
-        k.octave = o;
-        L.kp[i] = k;
-        status = kRefKeep;
-        it0 = 5;
-      } else if (pr.octave == kPreDiscard) {
-        it0 = 5;
-      } else if (pr.octave == kPreSingular) {
-        status = kRefSingular;
-        it0 = 5;
-      } else if (pr.octave == kPreMoved) {
-        s = pr.scale_level;
-        m = pr.local_y;
-        n = pr.local_x;
-        value = pr.interp_value;
-        it0 = 1;
-      }
-    }
-#endif
     if (value != value)  // deferred: the fp32 plane value
-      value = patched ? (double)pp[4] : (double)D[s * plane + (long long)m * w + n];
+      value = (double)D[s * plane + (long long)m * w + n];
     const double dval = EXACT ? 0.0 : fabs(value) * 0x1p-24;
     double d[27];
-    for (int it = it0; it < 5; ++it) {
+    for (int it = 0; it < 5; ++it) {
       double mx = 0;
-      if (it == 0 && patched) {
-        const float4 c0 = *reinterpret_cast<const float4*>(pp), c1 = *reinterpret_cast<const float4*>(pp + 4);
-        const float4 lf = *reinterpret_cast<const float4*>(pp + 8), rt = *reinterpret_cast<const float4*>(pp + 12);
-        const float4 ex = *reinterpret_cast<const float4*>(pp + 16);
-        const float v19[19] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w, ex.x,  // d(k, a, 1), 3k + a
-                               lf.x, lf.y, lf.z, lf.w, ex.y, rt.x, rt.y, rt.z, rt.w, ex.z};
-        constexpr int at[19] = {1, 4, 7, 10, 13, 16, 19, 22, 25, 9, 12, 15, 3, 21, 11, 14, 17, 5, 23};
-#pragma unroll
-        for (int j = 0; j < 27; ++j) d[j] = 0.0;
-#pragma unroll
-        for (int j = 0; j < 19; ++j) {
-          d[at[j]] = (double)v19[j];
-          mx = fmax(mx, fabs((double)v19[j]));
-        }
-      } else {
 #pragma unroll
       for (int k = 0; k < 3; ++k)
 #pragma unroll
@@ -130,7 +83,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
             d[k * 9 + a * 3 + c] = v;
             mx = fmax(mx, fabs(v));
           }
-      }
       // fp32 rounding of the fp64 value (<= |v| 2^-24) plus fp64 noise vs the reference.
       const double delta = EXACT ? 0.0 : mx * (0x1p-24 + 0x1p-40);
       const StepOut R = refine_step<!EXACT>(d, o, s, m, n, value, delta, dval, P.S, P.ND, h, w, P.thr, it == 4,
@@ -287,17 +239,6 @@ __device__ __forceinline__ bool keep_slot(const Pyramid& P, const int* __restric
   return k;
 }
 
-__global__ __launch_bounds__(256) void k_status_to_keep(const Pyramid P, const int* __restrict__ status,
-                                                        const unsigned* __restrict__ key,
-                                                        unsigned* __restrict__ keep, const unsigned* __restrict__ n,
-                                                        int cap, int own_lo, int own_hi,
-                                                        unsigned* __restrict__ blk) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= cap) return;
-  const int m = (int)min(*n, (unsigned)cap);
-  keep[i] = keep_slot(P, status, key, i, m, own_lo, own_hi, blk) ? 1u : 0u;
-}
-
 // ---------------------------------------------------------------------------
 // Compaction bounded by the device count (launch_keep_compact): the slots are
 // cut into tiles of kKeepTile; only the tiles up to the one holding slot m
@@ -393,16 +334,6 @@ __global__ __launch_bounds__(256) void k_keep_scatter(const unsigned* __restrict
     if (f && i < m) out[p] = kp[i];
     carry += ws[k & 1][0] + ws[k & 1][1] + ws[k & 1][2] + ws[k & 1][3];
   }
-}
-
-// keep: k_status_to_keep's flags (kept keypoint, in the owned rows).
-__global__ __launch_bounds__(256) void k_scatter_kp(const unsigned* __restrict__ keep,
-                                                    const unsigned* __restrict__ pos,
-                                                    const Keypoint* __restrict__ kp,
-                                                    const unsigned* __restrict__ n, int cap,
-                                                    Keypoint* __restrict__ out) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < cap && i < (int)min(*n, (unsigned)cap) && keep[i]) out[pos[i]] = kp[i];
 }
 
 // Candidate key of every kept keypoint, in keypoint order (the origin of a
@@ -597,14 +528,6 @@ hipError_t launch_refine_exact(const Pyramid& P, const RefineLaunch& R, hipStrea
   return hipGetLastError();
 }
 
-hipError_t launch_status_to_keep(const Pyramid& P, const int* status, const unsigned* key, unsigned* keep,
-                                 const unsigned* n, int cap, int own_lo, int own_hi, unsigned* blk, hipStream_t st) {
-  if (cap <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_status_to_keep, dim3((cap + 255) / 256), dim3(256), 0, st, P, status, key, keep, n, cap,
-                     own_lo, own_hi, blk);
-  return hipGetLastError();
-}
-
 hipError_t launch_keep_compact(const Pyramid& P, const int* status, const unsigned* key, unsigned* keep,
                                unsigned* pos, unsigned* tile, const unsigned* n, int cap, int own_lo, int own_hi,
                                unsigned* blk, const Keypoint* kp, Keypoint* out, hipStream_t st) {
@@ -614,13 +537,6 @@ hipError_t launch_keep_compact(const Pyramid& P, const int* status, const unsign
                      tile);
   hipLaunchKernelGGL(k_keep_scan, dim3(1), dim3(1024), 0, st, tile, n, cap);
   hipLaunchKernelGGL(k_keep_scatter, dim3(nt), dim3(256), 0, st, keep, tile, kp, n, cap, pos, out);
-  return hipGetLastError();
-}
-
-hipError_t launch_scatter_keypoints(const unsigned* keep, const unsigned* pos, const Keypoint* kp,
-                                    const unsigned* n, int cap, Keypoint* out, hipStream_t st) {
-  if (cap <= 0) return hipSuccess;
-  hipLaunchKernelGGL(k_scatter_kp, dim3((cap + 255) / 256), dim3(256), 0, st, keep, pos, kp, n, cap, out);
   return hipGetLastError();
 }
 

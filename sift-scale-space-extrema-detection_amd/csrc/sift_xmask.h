@@ -53,18 +53,13 @@ template <int NP>
 struct XWin {
   float hx[3][NP], hn[3][NP];  // 3-wide max / min of a row
   float ex[3][NP], en[3][NP];  // 2-wide (x-1, x+1) max / min (centre planes)
-  float cv[3][NP];             // the value (every plane: the outer ones feed the patch capture)
+  float cv[3][NP];             // the value itself
   float raw[3][NP];            // loaded, not yet derived rows
 };
 
 // Row reductions of one loaded row (all NP planes) into window slot K.
 template <int NP, int K>
 __device__ __forceinline__ void x_derive(XWin<NP>& Wn, const float (&src)[NP]) {
-#if defined(SIFT_X_PROBE) && SIFT_X_PROBE > 1  // timing probe: loads only
-#pragma unroll
-  for (int q = 0; q < NP; ++q) { Wn.hx[K][q] = src[q]; Wn.hn[K][q] = src[q]; }
-  return;
-#endif
 #pragma unroll
   for (int q = 0; q < NP; ++q) {
     const float v = src[q];

@@ -160,19 +160,33 @@ def test_planes_bit_exact_in_gpu_order(gpu_ctx, W, H, O, S, seed):
 
 
 @pytest.mark.timeout(300)
-def test_pass_kernels_record(gpu_ctx):
+@pytest.mark.parametrize("W,H", [(1920, 1080), (160, 120)], ids=["1920x1080", "160x120"])
+def test_pass_kernels_record(gpu_ctx, W, H):
     """sift_last_pass_kernels names each octave's launches (bench.py's
-    roofline.kernel): 1080p O4 S5 runs octave 0's staged tile kernel, octave 1
+    roofline.kernel): O4 S5 runs octave 0's staged tile kernel, octave 1
     (radii <= 12) the register-window kernel, octave 2 (radii <= 24) the
-    streamed one and octave 3 (radius 47) the split vertical pass + tiles."""
+    streamed one and octave 3 (radius 47) the split vertical pass + tiles.
+    Radii depend on octave and scale only, so 160x120 (octave 3: 40x30) takes
+    the same launches; there octave 3's planes are also checked against the
+    oracle in the HIP path's operation order, bit for bit."""
     p = sift_amd.make_params(4, 5)
-    gpu_ctx.build_scale_space(blob_image(1920, 1080, seed=3), p)
+    img = blob_image(W, H, seed=3)
+    gpu_ctx.build_scale_space(img, p)
     parts = dict(e.split(": ", 1) for e in gpu_ctx.pass_kernels().split("; "))
     assert sorted(parts) == ["o0", "o1", "o2", "o3"], parts
     assert parts["o0"].startswith("k_gauss_dog<octave0"), parts
     assert parts["o1"] == "k_gauss_rw<12>", parts
     assert parts["o2"] == "k_gauss_rw<24,true>", parts
     assert parts["o3"] == "k_gauss_vert + k_gauss_dog<64>", parts
+    if (W, H) == (160, 120):
+        from sift_amd.shard import octave_radii
+        assert max(octave_radii(p)[3]) == 47
+        r = orc.OracleRun(img, oracle_params(p), orc.CONV_SEPARABLE_FMA_VH, threads=host_threads())
+        assert tuple(r.dims[3]) == (30, 40)
+        for s in range(p.scales_per_octave + 3):
+            np.testing.assert_array_equal(gpu_ctx.plane(sift_amd.PLANE_GAUSS, 3, s), r.gauss[3][s].astype(np.float32))
+        for s in range(p.scales_per_octave + 2):
+            np.testing.assert_array_equal(gpu_ctx.plane(sift_amd.PLANE_DOG, 3, s), r.dog[3][s].astype(np.float32))
 
 
 @pytest.mark.timeout(600)
