@@ -23,15 +23,17 @@ using namespace sift;
 
 namespace {
 
-// Grow-only device buffer.
+// Grow-only device buffer, freed with its owner.
 struct DBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DBuf() = default;
+  DBuf(const DBuf&) = delete;
+  DBuf& operator=(const DBuf&) = delete;
+  ~DBuf() { release(); }
   hipError_t ensure(size_t need) {
     if (need <= bytes) return hipSuccess;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
+    release();
     size_t want = need + need / 4 + 256;
     hipError_t e = hipMalloc(&p, want);
     if (e == hipSuccess) bytes = want;
@@ -46,15 +48,17 @@ struct DBuf {
   T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-// Grow-only pinned host buffer (staging of host images and keypoint records).
+// Grow-only pinned host buffer (staging of host images and keypoint records), freed with its owner.
 struct HBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  HBuf() = default;
+  HBuf(const HBuf&) = delete;
+  HBuf& operator=(const HBuf&) = delete;
+  ~HBuf() { release(); }
   hipError_t ensure(size_t need) {
     if (need <= bytes) return hipSuccess;
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
+    release();
     size_t want = need + need / 4 + 256;
     hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
     if (e == hipSuccess) bytes = want;
@@ -67,25 +71,30 @@ struct HBuf {
   }
 };
 
+// f(i0, i1) over a split of [0, n) into up to `nt` ranges, one per thread
+// (the caller's included).
+template <class F>
+void par_for(size_t n, int nt, F f) {
+  std::vector<std::thread> th;
+  const size_t per = nt > 1 ? (n + nt - 1) / nt : n;
+  for (int t = 1; t < nt; ++t) {
+    const size_t i0 = std::min(n, t * per), i1 = std::min(n, (t + 1) * per);
+    if (i0 < i1) th.emplace_back(f, i0, i1);
+  }
+  f((size_t)0, std::min(n, per));
+  for (auto& x : th) x.join();
+}
+
+// Threads of a host copy of rows x width bytes: one below 4 MiB.
+int copy_threads(size_t rows, size_t width, int nt) { return rows * width < ((size_t)4 << 20) ? 1 : nt; }
+
 // Row copy between host buffers on up to `nt` threads (host memory bandwidth
 // of one core is well below what the DMA engines take from pinned memory).
 void par_copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t rows, int nt) {
-  auto part = [&](size_t r0, size_t r1) {
+  par_for(rows, copy_threads(rows, width, nt), [&](size_t r0, size_t r1) {
     for (size_t r = r0; r < r1; ++r)
       std::memcpy((char*)dst + r * dpitch, (const char*)src + r * spitch, width);
-  };
-  if (nt <= 1 || rows * width < ((size_t)4 << 20)) {
-    part(0, rows);
-    return;
-  }
-  std::vector<std::thread> th;
-  const size_t per = (rows + nt - 1) / nt;
-  for (int t = 1; t < nt; ++t) {
-    const size_t r0 = std::min(rows, t * per), r1 = std::min(rows, (t + 1) * per);
-    if (r0 < r1) th.emplace_back(part, r0, r1);
-  }
-  part(0, std::min(rows, per));
-  for (auto& x : th) x.join();
+  });
 }
 
 // Host rows -> pinned staging -> device, pipelined: each of nt host threads
@@ -95,7 +104,7 @@ void par_copy_rows(void* dst, size_t dpitch, const void* src, size_t spitch, siz
 hipError_t h2d_rows_staged(void* dev, void* stage, const void* src, size_t spitch, size_t width, size_t rows, int nt,
                            hipStream_t st) {
   std::atomic<int> err{0};
-  auto part = [&](size_t r0, size_t r1) {
+  par_for(rows, copy_threads(rows, width, nt), [&](size_t r0, size_t r1) {
     const size_t piece = std::max<size_t>(1, ((size_t)2 << 20) / width);
     for (size_t a = r0; a < r1; a += piece) {
       const size_t b = std::min(r1, a + piece);
@@ -104,19 +113,7 @@ hipError_t h2d_rows_staged(void* dev, void* stage, const void* src, size_t spitc
                          hipMemcpyHostToDevice, st) != hipSuccess)
         err = 1;
     }
-  };
-  if (nt <= 1 || rows * width < ((size_t)4 << 20)) {
-    part(0, rows);
-  } else {
-    std::vector<std::thread> th;
-    const size_t per = (rows + nt - 1) / nt;
-    for (int t = 1; t < nt; ++t) {
-      const size_t r0 = std::min(rows, t * per), r1 = std::min(rows, (t + 1) * per);
-      if (r0 < r1) th.emplace_back(part, r0, r1);
-    }
-    part(0, std::min(rows, per));
-    for (auto& x : th) x.join();
-  }
+  });
   return err ? hipErrorUnknown : hipSuccess;
 }
 
@@ -176,7 +173,8 @@ struct sift_ctx {
   bool detect_pending = false;   // sift_detect_device_async enqueued, sift_detect_wait not yet called
   bool begin_pending = false;    // sift_detect_begin_async enqueued, sift_detect_end_async not yet called
   bool detect_host_img = false;
-  ExtremaLaunch xl{};       // extrema launch state between prepare / scan / finish
+  ExtremaLaunch xl{};       // extrema launch state between prepare / scan / finish; xl.G is the bitmap
+                            // geometry of this extrema stage (bitmap_geometry), which every later launch copies
   int o_first = 0;          // first octave of the pyramid in use (sift_detect_from_seed: > 0)
   int scan_first = 0;       // first octave the extrema stage scans (>= o_first; sift_detect_from_seed_range)
   int planes_first = 0;     // first octave with Gaussian / DoG planes (below: only its successor's base)
@@ -184,9 +182,6 @@ struct sift_ctx {
   int xseed_h = 0, xseed_w = 0;  // SIFT_F_EXPORT_NEXT_SEED: the base of octave O
   bool has_xseed = false;
   bool has_origins = false; // kp_key holds the candidate key of every keypoint
-  std::vector<long long> x_word_off, x_row_off;
-  std::vector<int> x_nw, x_ww, x_woff;  // bitmap words per row, columns per word, column of bit 0
-  long long x_rows = 0;
   int x_nf = 0;             // leading octaves whose extrema decisions run fused into the Gaussian pass
   bool x_prepared = false;  // extrema_prepare already ran for this detection (fused octaves)
   // device memory
@@ -236,6 +231,20 @@ struct sift_ctx {
   sift_timings tm{};
   std::vector<double> oct_ms;      // per-octave Gaussian+DoG launch time of the last build
   std::vector<std::string> pass_kn; // per-octave pass kernels of the last build (sift_last_pass_kernels)
+
+  // The buffers free themselves; the caller has made `device` current and the stream is idle.
+  ~sift_ctx() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_go)
+      if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_pl)
+      if (e) (void)hipEventDestroy(e);
+    if (ev_heavy) (void)hipEventDestroy(ev_heavy);
+    if (ev_himg) (void)hipEventDestroy(ev_himg);
+    if (h_counters) (void)hipHostFree(h_counters);
+    if (stream && own_stream) (void)hipStreamDestroy(stream);
+  }
 };
 
 #define HIPCHK(call)                                                                        \
@@ -415,29 +424,6 @@ int sift_ctx_destroy(sift_ctx* ctx) {
   if (!ctx) return SIFT_E_ARG;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  DBuf* bufs[] = {&ctx->ambbitmap, &ctx->img, &ctx->seeds, &ctx->base0, &ctx->l64, &ctx->vsplit, &ctx->gauss, &ctx->dog, &ctx->wts, &ctx->bitmap,
-                  &ctx->rowcount, &ctx->rowoff, &ctx->amb_keys, &ctx->keep, &ctx->pos,
-                  &ctx->cand_keep, &ctx->cand_key, &ctx->cand_val, &ctx->status,
-                  &ctx->kp_tmp, &ctx->kp, &ctx->uncertain, &ctx->xseed, &ctx->kp_key, &ctx->counters,
-                  &ctx->temp, &ctx->rgba, &ctx->alpha, &ctx->display, &ctx->mm_parts, &ctx->merge_tab,
-                  &ctx->lowbitmap, &ctx->lowrowcount, &ctx->lowrowoff, &ctx->low_key, &ctx->low_val,
-                  &ctx->late_key, &ctx->late_val, &ctx->band_cnt, &ctx->band_first, &ctx->band_start,
-                  &ctx->perm, &ctx->kp_soa, &ctx->keep_tile};
-  for (DBuf* b : bufs) b->release();
-  for (auto& e : ctx->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto& e : ctx->ev_go)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->ev_heavy) (void)hipEventDestroy(ctx->ev_heavy);
-  ctx->himg.release();
-  ctx->hkp.release();
-  if (ctx->ev_himg) (void)hipEventDestroy(ctx->ev_himg);
-  ctx->hpl.release();
-  for (auto& e : ctx->ev_pl)
-    if (e) (void)hipEventDestroy(e);
-  if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
-  ctx->seedv.release();
-  if (ctx->stream && ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
   return SIFT_OK;
 }
@@ -773,9 +759,9 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
     if (o < nf) {
       const ExtremaLaunch& XL = ctx->xl;
       L.fuse = 1;
-      L.X.bitmap = XL.bitmap + XL.word_off[o];
-      L.X.rowcount = XL.rowcount + XL.row_off[o];
-      L.X.nw = ctx->x_nw[o];
+      L.X.bitmap = XL.bitmap + XL.G.word_off[o];
+      L.X.rowcount = XL.rowcount + XL.G.row_off[o];
+      L.X.nw = XL.G.nw[o];
       L.X.amb_keys = XL.amb_keys;
       L.X.counters = XL.counters;
       L.X.amb_cap = XL.amb_cap;
@@ -871,26 +857,52 @@ int sift_get_blur_level(sift_ctx* ctx, int kind, int o, int s, double* blur) {
   return SIFT_OK;
 }
 
-int sift_get_plane(sift_ctx* ctx, int kind, int o, int s, float* dst, size_t cap_px) {
-  if (!ctx || !dst) return SIFT_E_ARG;
-  if (ctx->dog_source == kNone) return set_err(ctx, SIFT_E_STATE, "no pyramid");
+// Device plane (kind, o, s) of the pyramid and its pixel count, for a
+// destination of cap_px pixels (too_small: the message when it is not enough).
+static int find_plane(sift_ctx* ctx, int kind, int o, int s, size_t cap_px, const char* too_small, const float** src,
+                      size_t* plane_px) {
   const Pyramid& P = ctx->P;
   if (o < 0 || o >= P.O) return set_err(ctx, SIFT_E_ARG, "octave out of range");
   if (o < ctx->planes_first) return set_err(ctx, SIFT_E_STATE, "octave not built (sift_detect_from_seed[_range])");
   const Octave& oc = P.oct[o];
   const size_t plane = (size_t)oc.h * oc.w;
-  if (cap_px < plane) return set_err(ctx, SIFT_E_CAPACITY, "destination too small");
-  const float* src = nullptr;
+  if (cap_px < plane) return set_err(ctx, SIFT_E_CAPACITY, too_small);
   if (kind == SIFT_PLANE_GAUSS) {
     if (!ctx->have_gauss) return set_err(ctx, SIFT_E_STATE, "Gaussian planes not materialised");
     if (s < 0 || s >= P.NS) return set_err(ctx, SIFT_E_ARG, "scale out of range");
-    src = ctx->gauss.as<float>() + oc.gauss_off + (size_t)s * plane;
+    *src = ctx->gauss.as<float>() + oc.gauss_off + (size_t)s * plane;
   } else if (kind == SIFT_PLANE_DOG) {
     if (s < 0 || s >= P.ND) return set_err(ctx, SIFT_E_ARG, "scale out of range");
-    src = ctx->dog.as<float>() + oc.dog_off + (size_t)s * plane;
+    *src = ctx->dog.as<float>() + oc.dog_off + (size_t)s * plane;
   } else {
     return set_err(ctx, SIFT_E_ARG, "bad plane kind");
   }
+  *plane_px = plane;
+  return SIFT_OK;
+}
+
+// The context after caller-supplied planes were queued for upload (sift_load_*).
+static int finish_load(sift_ctx* ctx, bool have_gauss) {
+  ctx->P.dog = ctx->dog.as<float>();
+  ctx->P.img = nullptr;
+  ctx->P.seeds = nullptr;
+  ctx->dog_source = kForeign;
+  ctx->o_first = 0;
+  ctx->scan_first = 0;
+  ctx->planes_first = 0;
+  ctx->have_gauss = have_gauss;
+  ctx->have_cand = false;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return SIFT_OK;
+}
+
+int sift_get_plane(sift_ctx* ctx, int kind, int o, int s, float* dst, size_t cap_px) {
+  if (!ctx || !dst) return SIFT_E_ARG;
+  if (ctx->dog_source == kNone) return set_err(ctx, SIFT_E_STATE, "no pyramid");
+  const float* src = nullptr;
+  size_t plane = 0;
+  const int rc = find_plane(ctx, kind, o, s, cap_px, "destination too small", &src, &plane);
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(d2h_staged(ctx, dst, src, plane * sizeof(float)));
   return SIFT_OK;
@@ -905,17 +917,7 @@ int sift_load_dog(sift_ctx* ctx, const float* planes, int width, int height, con
   HIPCHK(ctx->dog.ensure((size_t)tot * ctx->P.ND * sizeof(float)));
   HIPCHK(hipMemcpyAsync(ctx->dog.p, planes, (size_t)tot * ctx->P.ND * sizeof(float),
                         hipMemcpyHostToDevice, ctx->stream));
-  ctx->P.dog = ctx->dog.as<float>();
-  ctx->P.img = nullptr;
-  ctx->P.seeds = nullptr;
-  ctx->dog_source = kForeign;
-  ctx->o_first = 0;
-  ctx->scan_first = 0;
-  ctx->planes_first = 0;
-  ctx->have_gauss = false;
-  ctx->have_cand = false;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return SIFT_OK;
+  return finish_load(ctx, false);
 }
 
 int sift_load_scale_space(sift_ctx* ctx, const float* planes, int width, int height,
@@ -935,17 +937,7 @@ int sift_load_scale_space(sift_ctx* ctx, const float* planes, int width, int hei
     HIPCHK(launch_dog_from_gauss(ctx->gauss.as<float>() + oc.gauss_off, ctx->dog.as<float>() + oc.dog_off,
                                  (long long)oc.h * oc.w, P.ND, ctx->stream));
   }
-  ctx->P.dog = ctx->dog.as<float>();
-  ctx->P.img = nullptr;
-  ctx->P.seeds = nullptr;
-  ctx->dog_source = kForeign;
-  ctx->o_first = 0;
-  ctx->scan_first = 0;
-  ctx->planes_first = 0;
-  ctx->have_gauss = true;
-  ctx->have_cand = false;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return SIFT_OK;
+  return finish_load(ctx, true);
 }
 
 }  // extern "C"
@@ -975,38 +967,45 @@ constexpr int kRetry = 1;  // internal: a capacity overflowed, grow and run agai
 //   extrema_finish   row-count scan, ordered emission into cand_cap slots,
 //                    exact tie resolution (context stream).
 // Counts stay on the device.
+// Row / word geometry of the candidate bitmap: octaves < nf are decided in
+// the Gaussian pass (kFX-column words, bit 0 = column 1), the rest by the
+// scan (kXW-column words, bit 0 = column 0).
+static BitmapGeom bitmap_geometry(const Pyramid& P, int nf) {
+  BitmapGeom G{};
+  G.n_oct = P.O;
+  long long words = 0, rows = 0;
+  for (int o = 0; o < P.O; ++o) {
+    const bool f = o < nf;
+    G.nw[o] = f ? fused_words_per_row(P.oct[o].w) : extrema_words_per_row(P.oct[o].w);
+    G.ww[o] = f ? kFX : kXW;
+    G.woff[o] = f ? 1 : 0;
+    G.word_off[o] = words;
+    G.row_off[o] = (int)rows;
+    words += (long long)P.S * P.oct[o].h * G.nw[o];
+    rows += (long long)P.S * P.oct[o].h;
+  }
+  G.row_off[P.O] = (int)rows;
+  G.words_per_img = words;
+  G.rows_per_img = (int)rows;
+  return G;
+}
+
+// Rows of the bitmap over all images of the batch (image-major).
+static long long bitmap_rows(const sift_ctx* ctx) {
+  return (long long)ctx->xl.G.rows_per_img * std::max(1, ctx->P.nimg);
+}
+
 static int extrema_prepare(sift_ctx* ctx, hipStream_t st, int nf) {
   Pyramid& P = ctx->P;
   const bool exact_planes = ctx->dog_source == kForeign;
   unsigned* cnt = ctx->counters.as<unsigned>();
-  // Row / word geometry of the candidate bitmap: octaves < nf are decided in
-  // the Gaussian pass (kFX-column words, bit 0 = column 1), the rest by the
-  // scan (kXW-column words, bit 0 = column 0).
   ctx->x_nf = nf;
-  ctx->x_word_off.assign(P.O, 0);
-  ctx->x_row_off.assign(P.O, 0);
-  ctx->x_nw.assign(P.O, 0);
-  ctx->x_ww.assign(P.O, 0);
-  ctx->x_woff.assign(P.O, 0);
-  long long words = 0, rows = 0;
-  for (int o = 0; o < P.O; ++o) {
-    const bool f = o < nf;
-    const int nw = f ? fused_words_per_row(P.oct[o].w) : extrema_words_per_row(P.oct[o].w);
-    ctx->x_nw[o] = nw;
-    ctx->x_ww[o] = f ? kFX : kXW;
-    ctx->x_woff[o] = f ? 1 : 0;
-    ctx->x_word_off[o] = words;
-    ctx->x_row_off[o] = rows;
-    words += (long long)P.S * P.oct[o].h * nw;
-    rows += (long long)P.S * P.oct[o].h;
-  }
+  ExtremaLaunch& L = ctx->xl;
+  L = ExtremaLaunch{};
+  L.G = bitmap_geometry(P, nf);
   // A batch (P.nimg images) repeats the per-image words and rows image-major.
   const int ni = std::max(1, P.nimg);
-  ctx->xl.words_per_img = words;
-  ctx->xl.rows_per_img = (int)rows;
-  words *= ni;
-  rows *= ni;
-  ctx->x_rows = rows;
+  const long long words = L.G.words_per_img * ni, rows = bitmap_rows(ctx);
   {  // capacities: an estimate for this geometry, grown on overflow (settle_extrema)
     const long long est = std::min<long long>(
         std::max<long long>((long long)P.S * total_plane_px(ctx) * ni / 192, 65536), 0x7fffffffLL);
@@ -1040,21 +1039,11 @@ static int extrema_prepare(sift_ctx* ctx, hipStream_t st, int nf) {
   HIPCHK(launch_zero_words(cnt, kCntAll, ctx->rowcount.as<unsigned>(), rows + 1,
                            ctx->want_low ? ctx->lowrowcount.as<unsigned>() : nullptr, rows + 1, st));
   ctx->counters_zeroed = true;
-  ExtremaLaunch& L = ctx->xl;
-  const long long wpi = L.words_per_img;
-  const int rpi = L.rows_per_img;
-  L = ExtremaLaunch{};
-  L.words_per_img = wpi;
-  L.rows_per_img = rpi;
   L.exact_planes = exact_planes;
   L.c_lo = exact_planes ? t_up : t_dn;
   L.c_hi = exact_planes ? t_up : std::nextafter(t_up, INFINITY);
   L.bitmap = ctx->bitmap.as<unsigned long long>();
   L.rowcount = ctx->rowcount.as<unsigned>();
-  for (int o = 0; o < P.O; ++o) {
-    L.word_off[o] = ctx->x_word_off[o];
-    L.row_off[o] = (int)ctx->x_row_off[o];
-  }
   L.amb_keys = ctx->amb_keys.as<unsigned>();
   L.counters = cnt;
   L.amb_cap = ctx->amb_cap;
@@ -1077,76 +1066,58 @@ static int extrema_scan(sift_ctx* ctx, int o0, int o1, hipStream_t st) {
   return SIFT_OK;
 }
 
+// out = the exclusive prefix sums of in[0 .. n), on the context stream (scratch: ctx->temp).
+static hipError_t exclusive_sum(sift_ctx* ctx, unsigned* in, unsigned* out, int n) {
+  size_t tb = 0;
+  hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, ctx->stream);
+  if (e == hipSuccess) e = ctx->temp.ensure(tb);
+  if (e != hipSuccess) return e;
+  tb = ctx->temp.bytes;
+  return hipcub::DeviceScan::ExclusiveSum(ctx->temp.p, tb, in, out, n, ctx->stream);
+}
+
+// One ordered list from a bitmap of this extrema stage's geometry: the row
+// counts' exclusive scan into rowoff, then k_emit expands the rows' words in
+// order into keys / value / keep (cap slots); *n_out = the list's length,
+// written by k_emit (no 4-byte copy launch).
+static int emit_list(sift_ctx* ctx, const unsigned long long* bitmap, unsigned* rowcount, unsigned* rowoff,
+                     unsigned* keys, double* value, unsigned* keep, unsigned cap, unsigned* n_out, bool deferred) {
+  const Pyramid& P = ctx->P;
+  const long long rows = bitmap_rows(ctx);
+  HIPCHK(exclusive_sum(ctx, rowcount, rowoff, (int)(rows + 1)));
+  EmitLaunch E{};
+  E.G = ctx->xl.G;
+  E.o_first = std::min(std::max(ctx->o_first, ctx->scan_first), P.O - 1);  // rows of earlier octaves hold no decisions
+  E.bitmap = bitmap;
+  E.rowcount = rowcount;
+  E.rowoff = rowoff;
+  E.keys = keys;
+  E.value = value;
+  E.keep = keep;
+  E.cap = cap;
+  E.deferred = deferred;
+  E.n_out = n_out;
+  E.n_index = rows;
+  HIPCHK(launch_emit(P, E, ctx->stream));
+  return SIFT_OK;
+}
+
 static int extrema_finish(sift_ctx* ctx) {
   Pyramid& P = ctx->P;
   unsigned* cnt = ctx->counters.as<unsigned>();
-  const long long rows = ctx->x_rows;
-  size_t tb = 0;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, ctx->rowcount.as<unsigned>(), ctx->rowoff.as<unsigned>(),
-                                          (int)(rows + 1), ctx->stream));
-  HIPCHK(ctx->temp.ensure(tb));
-  tb = ctx->temp.bytes;
-  HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->temp.p, tb, ctx->rowcount.as<unsigned>(), ctx->rowoff.as<unsigned>(),
-                                          (int)(rows + 1), ctx->stream));
-  {
-    EmitLaunch E{};
-    E.n_out = cnt + kCntN;  // the list's length, written by k_emit (no 4-byte copy launch)
-    E.n_index = rows;
-    E.n_oct = P.O;
-    E.o_first = std::min(std::max(ctx->o_first, ctx->scan_first), P.O - 1);  // rows of earlier octaves hold no decisions
-    for (int o = 0; o < P.O; ++o) {
-      E.row_off[o] = (int)ctx->x_row_off[o];
-      E.word_off[o] = ctx->x_word_off[o];
-      E.nw[o] = ctx->x_nw[o];
-      E.ww[o] = ctx->x_ww[o];
-      E.woff[o] = ctx->x_woff[o];
-    }
-    E.row_off[P.O] = ctx->xl.rows_per_img;
-    E.words_per_img = ctx->xl.words_per_img;
-    E.bitmap = ctx->bitmap.as<unsigned long long>();
-    E.rowcount = ctx->rowcount.as<unsigned>();
-    E.rowoff = ctx->rowoff.as<unsigned>();
-    E.keys = ctx->cand_key.as<unsigned>();
-    E.value = ctx->cand_val.as<double>();
-    E.keep = ctx->cand_keep.as<unsigned>();
-    E.cap = ctx->cand_cap;
-    // Deferred values (SIFT_DEFER_VALUES=0: gathered here, experiments): the
-    // refinement reads each candidate's plane value from the DoG plane, with
-    // the 3x3x3 neighbourhood it gathers there anyway.
-    static const int defer = exp_knob("SIFT_DEFER_VALUES", 1);
-    E.deferred = defer != 0;
-    HIPCHK(launch_emit(P, E, ctx->stream));
-  }
+  // Deferred values (SIFT_DEFER_VALUES=0: gathered here, experiments): the
+  // refinement reads each candidate's plane value from the DoG plane, with
+  // the 3x3x3 neighbourhood it gathers there anyway.
+  static const int defer = exp_knob("SIFT_DEFER_VALUES", 1);
+  int rc = emit_list(ctx, ctx->bitmap.as<unsigned long long>(), ctx->rowcount.as<unsigned>(),
+                     ctx->rowoff.as<unsigned>(), ctx->cand_key.as<unsigned>(), ctx->cand_val.as<double>(),
+                     ctx->cand_keep.as<unsigned>(), ctx->cand_cap, cnt + kCntN, defer != 0);
+  if (rc) return rc;
   if (ctx->want_low) {  // the certain low-contrast extrema, in order (same scan + emission as the candidates)
-    size_t lb = 0;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, lb, ctx->lowrowcount.as<unsigned>(),
-                                            ctx->lowrowoff.as<unsigned>(), (int)(rows + 1), ctx->stream));
-    HIPCHK(ctx->temp.ensure(lb));
-    lb = ctx->temp.bytes;
-    HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->temp.p, lb, ctx->lowrowcount.as<unsigned>(),
-                                            ctx->lowrowoff.as<unsigned>(), (int)(rows + 1), ctx->stream));
-    EmitLaunch E{};
-    E.n_out = cnt + kCntLowSure;
-    E.n_index = rows;
-    E.n_oct = P.O;
-    E.o_first = std::min(std::max(ctx->o_first, ctx->scan_first), P.O - 1);  // rows of earlier octaves hold no decisions
-    for (int o = 0; o < P.O; ++o) {
-      E.row_off[o] = (int)ctx->x_row_off[o];
-      E.word_off[o] = ctx->x_word_off[o];
-      E.nw[o] = ctx->x_nw[o];
-      E.ww[o] = ctx->x_ww[o];
-      E.woff[o] = ctx->x_woff[o];
-    }
-    E.row_off[P.O] = ctx->xl.rows_per_img;
-    E.words_per_img = ctx->xl.words_per_img;
-    E.bitmap = ctx->lowbitmap.as<unsigned long long>();
-    E.rowcount = ctx->lowrowcount.as<unsigned>();
-    E.rowoff = ctx->lowrowoff.as<unsigned>();
-    E.keys = ctx->low_key.as<unsigned>();
-    E.value = ctx->low_val.as<double>();
-    E.keep = nullptr;
-    E.cap = ctx->low_cap;
-    HIPCHK(launch_emit(P, E, ctx->stream));
+    rc = emit_list(ctx, ctx->lowbitmap.as<unsigned long long>(), ctx->lowrowcount.as<unsigned>(),
+                   ctx->lowrowoff.as<unsigned>(), ctx->low_key.as<unsigned>(), ctx->low_val.as<double>(), nullptr,
+                   ctx->low_cap, cnt + kCntLowSure, false);
+    if (rc) return rc;
   }
   ExactLaunch X{};
   X.late_keys = ctx->want_low ? ctx->late_key.as<unsigned>() : nullptr;
@@ -1159,33 +1130,16 @@ static int extrema_finish(sift_ctx* ctx) {
   X.keep = ctx->cand_keep.as<unsigned>();
   X.value = ctx->cand_val.as<double>();
   X.counters = cnt;
+  X.G = ctx->xl.G;
+  // List positions from the emission geometry (SIFT_XPOS=0: a binary search
+  // over the keys, experiments; the word pass always takes the geometry).
   static const int xpos = exp_knob("SIFT_XPOS", 1);
-  if (xpos) {  // list positions from the emission geometry instead of a binary search
+  if (xpos || ctx->x_words) {
     X.bitmap = ctx->bitmap.as<unsigned long long>();
     X.rowoff = ctx->rowoff.as<unsigned>();
-    X.words_per_img = ctx->xl.words_per_img;
-    X.rows_per_img = ctx->xl.rows_per_img;
-    for (int o = 0; o < P.O; ++o) {
-      X.row_off[o] = (int)ctx->x_row_off[o];
-      X.word_off[o] = ctx->x_word_off[o];
-      X.nw[o] = ctx->x_nw[o];
-      X.ww[o] = ctx->x_ww[o];
-      X.woff[o] = ctx->x_woff[o];
-    }
   }
   if (ctx->x_words) {
     X.ambbitmap = ctx->ambbitmap.as<unsigned long long>();
-    X.bitmap = ctx->bitmap.as<unsigned long long>();
-    X.rowoff = ctx->rowoff.as<unsigned>();
-    X.words_per_img = ctx->xl.words_per_img;
-    X.rows_per_img = ctx->xl.rows_per_img;
-    for (int o = 0; o < P.O; ++o) {
-      X.row_off[o] = (int)ctx->x_row_off[o];
-      X.word_off[o] = ctx->x_word_off[o];
-      X.nw[o] = ctx->x_nw[o];
-      X.ww[o] = ctx->x_ww[o];
-      X.woff[o] = ctx->x_woff[o];
-    }
     HIPCHK(launch_exact_words(P, X, ctx->stream));
   } else {
     HIPCHK(launch_exact_extrema(P, X, ctx->stream));
@@ -1291,16 +1245,14 @@ static int refine_enqueue(sift_ctx* ctx) {
     static const int band_order = exp_knob("SIFT_BAND_ORDER", 1);
     if (band_order && ctx->slots_rows) {
       BandOrder B{};
-      B.n_oct = P.O;
+      B.G = ctx->xl.G;
       B.S = P.S;
       int items = 0;
       for (int o = 0; o < P.O; ++o) {
         B.item_off[o] = items;
-        B.row_off[o] = (int)ctx->x_row_off[o];
         items += P.S * ((P.oct[o].h + kBandRows - 1) / kBandRows);
       }
       B.item_off[P.O] = items;
-      B.rows_per_img = ctx->xl.rows_per_img;
       items *= std::max(1, P.nimg);  // image-major
       B.n_items = items;
       HIPCHK(ctx->band_cnt.ensure((size_t)items * sizeof(unsigned)));
@@ -1314,13 +1266,7 @@ static int refine_enqueue(sift_ctx* ctx) {
       B.perm = ctx->perm.as<unsigned>();
       B.cap = cap;
       HIPCHK(launch_band_items(P, B, ctx->stream));
-      size_t tb = 0;
-      HIPCHK(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, B.count, ctx->band_start.as<unsigned>(), items,
-                                              ctx->stream));
-      HIPCHK(ctx->temp.ensure(tb));
-      tb = ctx->temp.bytes;
-      HIPCHK(hipcub::DeviceScan::ExclusiveSum(ctx->temp.p, tb, B.count, ctx->band_start.as<unsigned>(), items,
-                                              ctx->stream));
+      HIPCHK(exclusive_sum(ctx, B.count, ctx->band_start.as<unsigned>(), items));
       HIPCHK(launch_band_fill(P, B, ctx->stream));
       R.perm = B.perm;
     }
@@ -1415,17 +1361,8 @@ int sift_copy_candidates(sift_ctx* ctx, sift_extremum* out, size_t cap, size_t* 
   size_t j = 0;
   for (size_t i = 0; i < n; ++i) {
     if (!keep[i]) continue;
-    unsigned k = keys[i];
-    int o = 0;
-    while (o + 1 < P.O && k >= P.oct[o + 1].key_off) ++o;
-    unsigned r = k - P.oct[o].key_off;
-    const unsigned plane = (unsigned)P.oct[o].h * (unsigned)P.oct[o].w;
-    const int s = (int)(r / plane) + 1;
-    r -= (unsigned)(s - 1) * plane;
-    out[j].octave = o;
-    out[j].scale = s;
-    out[j].y = (int)(r / (unsigned)P.oct[o].w);
-    out[j].x = (int)(r % (unsigned)P.oct[o].w);
+    int b;
+    decode_key(P, keys[i], b, out[j].octave, out[j].scale, out[j].y, out[j].x);
     out[j].value = vals[i];
     ++j;
   }
@@ -1462,14 +1399,8 @@ int sift_copy_low_contrast(sift_ctx* ctx, sift_extremum* out, size_t cap, size_t
   std::inplace_merge(idx.begin(), idx.begin() + ns, idx.end(), [&](size_t a, size_t b) { return k[a] < k[b]; });
   const Pyramid& P = ctx->P;
   for (size_t j = 0; j < n; ++j) {
-    const unsigned key = k[idx[j]];
-    int o = 0;
-    while (o + 1 < P.O && key >= P.oct[o + 1].key_off) ++o;
-    const unsigned plane = (unsigned)P.oct[o].h * (unsigned)P.oct[o].w, r = key - P.oct[o].key_off;
-    out[j].octave = o;
-    out[j].scale = (int)(r / plane) + 1;
-    out[j].y = (int)((r % plane) / (unsigned)P.oct[o].w);
-    out[j].x = (int)((r % plane) % (unsigned)P.oct[o].w);
+    int b;
+    decode_key(P, k[idx[j]], b, out[j].octave, out[j].scale, out[j].y, out[j].x);
     out[j].value = v[idx[j]];
   }
   return SIFT_OK;
@@ -1569,7 +1500,7 @@ int sift_copy_keypoints_soa(sift_ctx* ctx, int32_t* ints, double* reals, size_t 
   HIPCHK(hipMemcpyAsync(ctx->hkp.p, ctx->kp.p, n * sizeof(sift_keypoint), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   const sift_keypoint* k = (const sift_keypoint*)ctx->hkp.p;
-  auto part = [&](size_t i0, size_t i1) {
+  par_for(n, n >= 65536 ? host_threads() : 1, [&](size_t i0, size_t i1) {
     for (size_t i = i0; i < i1; ++i) {
       ints[4 * i] = k[i].octave;
       ints[4 * i + 1] = k[i].scale_level;
@@ -1580,16 +1511,7 @@ int sift_copy_keypoints_soa(sift_ctx* ctx, int32_t* ints, double* reals, size_t 
       reals[4 * i + 2] = k[i].abs_y;
       reals[4 * i + 3] = k[i].interp_value;
     }
-  };
-  const int nt = n >= 65536 ? host_threads() : 1;
-  std::vector<std::thread> th;
-  const size_t per = (n + nt - 1) / nt;
-  for (int t = 1; t < nt; ++t) {
-    const size_t i0 = std::min(n, t * per), i1 = std::min(n, (t + 1) * per);
-    if (i0 < i1) th.emplace_back(part, i0, i1);
-  }
-  part(0, std::min(n, per));
-  for (auto& x : th) x.join();
+  });
   return SIFT_OK;
 }
 
@@ -1671,12 +1593,24 @@ static int detect_common(sift_ctx* ctx, const float* img_host, const float* img_
   return rc ? rc : detect_finish(ctx, out, cap, n_out);
 }
 
+// An asynchronous entry point starts only on a context with no detection in flight.
+static int check_idle(sift_ctx* ctx) {
+  if (ctx->detect_pending || ctx->begin_pending)
+    return set_err(ctx, SIFT_E_STATE, "a detection is already in flight on this context");
+  return SIFT_OK;
+}
+
+static int check_batch(sift_ctx* ctx, int n_images, size_t image_stride_px, int height, size_t stride_px) {
+  if (n_images < 1 || (n_images > 1 && image_stride_px < (size_t)height * stride_px))
+    return set_err(ctx, SIFT_E_ARG, "n_images < 1 or overlapping images");
+  return SIFT_OK;
+}
+
 int sift_detect_device_async(sift_ctx* ctx, const float* d_img, int width, int height, size_t stride_px,
                              const sift_params* p) {
   if (!ctx) return SIFT_E_ARG;
   (void)hipSetDevice(ctx->device);
-  if (ctx->detect_pending || ctx->begin_pending)
-    return set_err(ctx, SIFT_E_STATE, "a detection is already in flight on this context");
+  if (int rc = check_idle(ctx)) return rc;
   return detect_enqueue(ctx, nullptr, d_img, width, height, stride_px, p);
 }
 
@@ -1684,10 +1618,8 @@ int sift_detect_batch_device_async(sift_ctx* ctx, const float* d_imgs, int n_ima
                                    int width, int height, size_t stride_px, const sift_params* p) {
   if (!ctx) return SIFT_E_ARG;
   (void)hipSetDevice(ctx->device);
-  if (n_images < 1 || (n_images > 1 && image_stride_px < (size_t)height * stride_px))
-    return set_err(ctx, SIFT_E_ARG, "n_images < 1 or overlapping images");
-  if (ctx->detect_pending || ctx->begin_pending)
-    return set_err(ctx, SIFT_E_STATE, "a detection is already in flight on this context");
+  if (int rc = check_batch(ctx, n_images, image_stride_px, height, stride_px)) return rc;
+  if (int rc = check_idle(ctx)) return rc;
   return detect_enqueue(ctx, nullptr, d_imgs, width, height, stride_px, p, n_images, image_stride_px);
 }
 
@@ -1695,10 +1627,8 @@ int sift_detect_batch(sift_ctx* ctx, const float* imgs, int n_images, size_t ima
                       size_t stride_px, const sift_params* p, sift_keypoint* out, size_t cap, size_t* n_out) {
   if (!ctx) return SIFT_E_ARG;
   (void)hipSetDevice(ctx->device);
-  if (n_images < 1 || (n_images > 1 && image_stride_px < (size_t)height * stride_px))
-    return set_err(ctx, SIFT_E_ARG, "n_images < 1 or overlapping images");
-  if (ctx->detect_pending || ctx->begin_pending)
-    return set_err(ctx, SIFT_E_STATE, "a detection is already in flight on this context");
+  if (int rc = check_batch(ctx, n_images, image_stride_px, height, stride_px)) return rc;
+  if (int rc = check_idle(ctx)) return rc;
   const int rc = detect_enqueue(ctx, imgs, nullptr, width, height, stride_px, p, n_images, image_stride_px);
   return host_image_exit(ctx, rc ? rc : detect_finish(ctx, out, cap, n_out));
 }
@@ -1714,8 +1644,7 @@ int sift_detect_begin_async(sift_ctx* ctx, const float* d_img, int width, int he
                             const sift_params* p) {
   if (!ctx) return SIFT_E_ARG;
   (void)hipSetDevice(ctx->device);
-  if (ctx->detect_pending || ctx->begin_pending)
-    return set_err(ctx, SIFT_E_STATE, "a detection is already in flight on this context");
+  if (int rc = check_idle(ctx)) return rc;
   return detect_begin(ctx, nullptr, d_img, width, height, stride_px, p);
 }
 
@@ -2004,23 +1933,10 @@ static int plane_image_common(sift_ctx* ctx, int kind, int o, int s, int mode, d
   if (!ctx || !dst) return SIFT_E_ARG;
   if (ctx->dog_source == kNone) return set_err(ctx, SIFT_E_STATE, "no pyramid");
   if (mode < SIFT_DISPLAY_PLAIN || mode > SIFT_DISPLAY_SAMPLED) return set_err(ctx, SIFT_E_ARG, "bad display mode");
-  const Pyramid& P = ctx->P;
-  if (o < 0 || o >= P.O) return set_err(ctx, SIFT_E_ARG, "octave out of range");
-  if (o < ctx->planes_first) return set_err(ctx, SIFT_E_STATE, "octave not built (sift_detect_from_seed[_range])");
-  const Octave& oc = P.oct[o];
-  const size_t plane = (size_t)oc.h * oc.w;
-  if (cap_bytes < plane * 4) return set_err(ctx, SIFT_E_CAPACITY, "destination too small (4 bytes per pixel)");
   const float* src = nullptr;
-  if (kind == SIFT_PLANE_GAUSS) {
-    if (!ctx->have_gauss) return set_err(ctx, SIFT_E_STATE, "Gaussian planes not materialised");
-    if (s < 0 || s >= P.NS) return set_err(ctx, SIFT_E_ARG, "scale out of range");
-    src = ctx->gauss.as<float>() + oc.gauss_off + (size_t)s * plane;
-  } else if (kind == SIFT_PLANE_DOG) {
-    if (s < 0 || s >= P.ND) return set_err(ctx, SIFT_E_ARG, "scale out of range");
-    src = ctx->dog.as<float>() + oc.dog_off + (size_t)s * plane;
-  } else {
-    return set_err(ctx, SIFT_E_ARG, "bad plane kind");
-  }
+  size_t plane = 0;
+  const int rc = find_plane(ctx, kind, o, s, cap_bytes / 4, "destination too small (4 bytes per pixel)", &src, &plane);
+  if (rc) return rc;
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(ctx->mm_parts.ensure((size_t)plane_image_parts((long long)plane) * sizeof(float2)));
   unsigned* out = reinterpret_cast<unsigned*>(dst);
@@ -2116,15 +2032,13 @@ int sift_keypoint_origins(sift_ctx* ctx, int32_t* out, size_t cap, size_t* n_out
                         ctx->stream));
   HIPCHK(hipStreamSynchronize(ctx->stream));
   const Pyramid& P = ctx->P;
-  for (size_t i = 0; i < keys.size(); ++i) {  // key = key_off(o) + (s-1) h w + y w + x
-    int o = P.O - 1;
-    while (o > 0 && keys[i] < P.oct[o].key_off) --o;
-    const Octave& oc = P.oct[o];
-    const unsigned plane = (unsigned)oc.h * (unsigned)oc.w, r = keys[i] - oc.key_off;
+  for (size_t i = 0; i < keys.size(); ++i) {
+    int b, o, s, y, x;
+    decode_key(P, keys[i], b, o, s, y, x);
     out[4 * i + 0] = o;
-    out[4 * i + 1] = (int32_t)(r / plane) + 1;
-    out[4 * i + 2] = (int32_t)((r % plane) / (unsigned)oc.w) + ((P.row0 * 2) >> o);
-    out[4 * i + 3] = (int32_t)((r % plane) % (unsigned)oc.w);
+    out[4 * i + 1] = s;
+    out[4 * i + 2] = y + ((P.row0 * 2) >> o);  // whole-image octave row
+    out[4 * i + 3] = x;
   }
   return SIFT_OK;
 }

@@ -85,7 +85,7 @@ __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? l
 
 // Candidate sort key -> (image, octave, scale, y, x): key = b kpi + the
 // image-local key of (o, s, y, x).
-__device__ __forceinline__ void decode_key(const Pyramid& P, unsigned key, int& b, int& o, int& s, int& y,
+__host__ __device__ __forceinline__ void decode_key(const Pyramid& P, unsigned key, int& b, int& o, int& s, int& y,
                                            int& x) {
   b = 0;
   if (P.nimg > 1) {

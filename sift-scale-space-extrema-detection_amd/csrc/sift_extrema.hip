@@ -158,7 +158,7 @@ __device__ __forceinline__ void x_scan(const Pyramid& P, const ExtremaLaunch& L,
   U.y1 = y1;
   U.lane = threadIdx.x & 63;
   U.xw = xw;
-  U.nw = L.nw[o];
+  U.nw = L.G.nw[o];
   U.s_first = s_first;
   U.o = o;
   const int x = xw * kXW - 1 + U.lane;
@@ -168,8 +168,8 @@ __device__ __forceinline__ void x_scan(const Pyramid& P, const ExtremaLaunch& L,
   U.base = P.dog + b * P.dog_bstride + oc.dog_off + (long long)(s_first - 1) * U.plane;
   U.rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(U.base), 0, -1, 0x00020000);
   U.key_base = (unsigned)b * P.kpi + oc.key_off + (unsigned)(s_first - 1) * (unsigned)U.plane;
-  const long long wb = b * L.words_per_img + L.word_off[o] + (long long)(s_first - 1) * oc.h * U.nw;
-  const long long rb = (long long)b * L.rows_per_img + L.row_off[o] + (s_first - 1) * oc.h;
+  const long long wb = b * L.G.words_per_img + L.G.word_off[o] + (long long)(s_first - 1) * oc.h * U.nw;
+  const long long rb = (long long)b * L.G.rows_per_img + L.G.row_off[o] + (s_first - 1) * oc.h;
   U.bitmap = L.bitmap + wb;
   U.word0 = wb;
   U.boff = ((long long)U.lane * U.h) * U.nw + xw;
@@ -236,11 +236,11 @@ __global__ __launch_bounds__(256, SIFT_XMINW) void k_extrema(const Pyramid P, co
   const int b = ug / span;
   const int u = L.u_begin + ug - b * span;
   int o = 0;
-  while (o + 1 < L.n_oct && u >= L.unit_off[o + 1]) ++o;
+  while (o + 1 < L.G.n_oct && u >= L.unit_off[o + 1]) ++o;
   int loc = u - L.unit_off[o];
   const int g = loc % L.ng;
   loc /= L.ng;
-  const int nw = L.nw[o];
+  const int nw = L.G.nw[o];
   const int xw = loc % nw, strip = loc / nw;
   const int y0 = 1 + strip * kXRows, y1 = min(P.oct[o].h - 2, y0 + kXRows - 1);
   const int per = P.S / L.ng, rem = P.S % L.ng;
@@ -261,17 +261,17 @@ __global__ __launch_bounds__(256, SIFT_XMINW) void k_extrema(const Pyramid P, co
 __global__ __launch_bounds__(256) void k_emit(const Pyramid P, const EmitLaunch E) {
   if (E.n_out && blockIdx.x == 0 && threadIdx.x == 0) *E.n_out = E.rowoff[E.n_index];
   const int lane = threadIdx.x & 63;
-  const int rpi = E.row_off[E.n_oct];
-  const int r0 = E.row_off[E.o_first], act = rpi - r0;  // rows per image with decisions
+  const int rpi = E.G.row_off[E.G.n_oct];
+  const int r0 = E.G.row_off[E.o_first], act = rpi - r0;  // rows per image with decisions
   const int ga = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (ga >= act * P.nimg) return;
   const int im = ga / act, gl = r0 + (ga - im * act);
   const int g = im * rpi + gl;  // global row (image-major)
   int o = E.o_first;
-  while (o + 1 < E.n_oct && gl >= E.row_off[o + 1]) ++o;
+  while (o + 1 < E.G.n_oct && gl >= E.G.row_off[o + 1]) ++o;
   const Octave& oc = P.oct[o];
   const int h = oc.h, w = oc.w;
-  const int row = gl - E.row_off[o];  // (s-1)*h + y within the octave
+  const int row = gl - E.G.row_off[o];  // (s-1)*h + y within the octave
   const int s = row / h + 1, y = row - (s - 1) * h;
   if (y < 1 || y > h - 2) return;
   const unsigned cnt = E.rowcount[g];
@@ -280,8 +280,8 @@ __global__ __launch_bounds__(256) void k_emit(const Pyramid P, const EmitLaunch 
   const long long plane = (long long)h * w;
   const float* __restrict__ Dc = P.dog + im * P.dog_bstride + oc.dog_off + s * plane + (long long)y * w;
   const unsigned kbase = (unsigned)im * P.kpi + oc.key_off + (unsigned)(s - 1) * (unsigned)plane + (unsigned)y * (unsigned)w;
-  const int nw = E.nw[o];
-  const long long wrow = im * E.words_per_img + E.word_off[o] + (long long)row * nw;
+  const int nw = E.G.nw[o];
+  const long long wrow = im * E.G.words_per_img + E.G.word_off[o] + (long long)row * nw;
   const unsigned long long* bm = E.bitmap + wrow;
   for (int xw0 = 0; xw0 < nw; xw0 += 64) {
     const int xw = xw0 + lane;
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256) void k_emit(const Pyramid P, const EmitLaunch 
       if (lane >= off) inc += t;
     }
     unsigned pos = base + inc - c;
-    const int xb = xw * E.ww[o] + E.woff[o];  // column of bit 0
+    const int xb = xw * E.G.ww[o] + E.G.woff[o];  // column of bit 0
     while (word) {
       const int b = __ffsll((long long)word) - 1;
       word &= word - 1;
@@ -327,8 +327,8 @@ __global__ __launch_bounds__(64) void k_exact_extrema(const Pyramid P, const Exa
     if (X.bitmap) {  // the row's offset + the candidate bits before x (parallel loads, one wave reduction)
       const int h = P.oct[o].h;
       const int rr = (s - 1) * h + y;
-      const long long wbase = im * X.words_per_img + X.word_off[o] + (long long)rr * X.nw[o];
-      const int xr = x - X.woff[o], xw = xr / X.ww[o], b = xr - xw * X.ww[o];
+      const long long wbase = im * X.G.words_per_img + X.G.word_off[o] + (long long)rr * X.G.nw[o];
+      const int xr = x - X.G.woff[o], xw = xr / X.G.ww[o], b = xr - xw * X.G.ww[o];
       unsigned c = 0;
       for (int w = (int)threadIdx.x; w <= xw; w += 64) {
         unsigned long long word = X.bitmap[wbase + w];
@@ -337,7 +337,7 @@ __global__ __launch_bounds__(64) void k_exact_extrema(const Pyramid P, const Exa
       }
 #pragma unroll
       for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
-      idx = X.rowoff[(long long)im * X.rows_per_img + X.row_off[o] + rr] + c;
+      idx = X.rowoff[(long long)im * X.G.rows_per_img + X.G.row_off[o] + rr] + c;
     } else {  // binary search
       unsigned lo = 0, hi = n;
       while (lo < hi) {
@@ -400,13 +400,13 @@ __global__ __launch_bounds__(kWordThreads) void k_exact_words(const Pyramid P, c
   double* Lb = smem + 12 * VS;   // [t * 3 + a][c], c < 64
   for (unsigned j = blockIdx.x; j < nwd; j += gridDim.x) {
     const long long gw = X.amb_keys[j];
-    const int im = (int)(gw / X.words_per_img);
-    const long long lw = gw - im * X.words_per_img;
+    const int im = (int)(gw / X.G.words_per_img);
+    const long long lw = gw - im * X.G.words_per_img;
     int o = 0;
-    while (o + 1 < P.O && lw >= X.word_off[o + 1]) ++o;
+    while (o + 1 < P.O && lw >= X.G.word_off[o + 1]) ++o;
     const Octave& oc = P.oct[o];
-    const int h = oc.h, w = oc.w, nw = X.nw[o];
-    const long long rel = lw - X.word_off[o];
+    const int h = oc.h, w = oc.w, nw = X.G.nw[o];
+    const long long rel = lw - X.G.word_off[o];
     const int rr = (int)(rel / nw), xw = (int)(rel - (long long)rr * nw);
     const int s = rr / h + 1, y = rr - (s - 1) * h;
     const unsigned long long amb = X.ambbitmap[gw], cand = X.bitmap[gw];
@@ -415,7 +415,7 @@ __global__ __launch_bounds__(kWordThreads) void k_exact_words(const Pyramid P, c
     for (int q = lane; q < xw; q += 64) c += (unsigned)__popcll(X.bitmap[gw - xw + q]);  // (each wave the same)
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) c += __shfl_xor(c, off);
-    const unsigned base = X.rowoff[(long long)im * X.rows_per_img + X.row_off[o] + rr] + c;
+    const unsigned base = X.rowoff[(long long)im * X.G.rows_per_img + X.G.row_off[o] + rr] + c;
     const int x0 = xw * kXW - 1;  // column of lane 0 (lanes 1..62 <-> bits 0..61)
     // Exact decision of the pixel at lane ln (bit ln - 1) from the fp64 DoG
     // value v and its 26 neighbours (nb(k, a, dc)), written at its slot.
@@ -536,22 +536,25 @@ hipError_t launch_exact_words(const Pyramid& P, ExactLaunch X, hipStream_t st) {
   return hipGetLastError();
 }
 
-static void extrema_unit_table(const Pyramid& P, int* unit_off, int* nw) {
+static void extrema_unit_table(const Pyramid& P, int* unit_off) {
   const int ng = (P.S + kXMaxGroup - 1) / kXMaxGroup;
   int units = 0;
   for (int o = 0; o < P.O; ++o) {
     const Octave& oc = P.oct[o];
     unit_off[o] = units;
-    nw[o] = extrema_words_per_row(oc.w);
-    if (oc.h >= 3 && oc.w >= 3 && P.S >= 1) units += ng * nw[o] * ((oc.h - 2 + kXRows - 1) / kXRows);
+    if (oc.h >= 3 && oc.w >= 3 && P.S >= 1)
+      units += ng * extrema_words_per_row(oc.w) * ((oc.h - 2 + kXRows - 1) / kXRows);
   }
   unit_off[P.O] = units;
 }
 
 hipError_t launch_extrema(const Pyramid& P, ExtremaLaunch& L, hipStream_t st, int o_begin, int o_end) {
-  L.n_oct = P.O;
+  // a unit's word and strip come from its index by the scan's word count
+  if (L.G.n_oct != P.O || o_begin < 0 || o_end > P.O) return hipErrorInvalidValue;
+  for (int o = o_begin; o < o_end; ++o)
+    if (L.G.nw[o] != extrema_words_per_row(P.oct[o].w) || L.G.ww[o] != kXW) return hipErrorInvalidValue;
   L.ng = (P.S + kXMaxGroup - 1) / kXMaxGroup;
-  extrema_unit_table(P, L.unit_off, L.nw);
+  extrema_unit_table(P, L.unit_off);
   L.u_begin = L.unit_off[o_begin];
   L.u_end = L.unit_off[o_end];
   if (L.u_end <= L.u_begin) return hipSuccess;
@@ -580,8 +583,8 @@ hipError_t launch_extrema(const Pyramid& P, ExtremaLaunch& L, hipStream_t st, in
 }
 
 hipError_t launch_emit(const Pyramid& P, const EmitLaunch& E, hipStream_t st) {
-  if (E.o_first < 0 || E.o_first >= E.n_oct) return hipErrorInvalidValue;
-  const int rows = (E.row_off[E.n_oct] - E.row_off[E.o_first]) * std::max(1, P.nimg);
+  if (E.o_first < 0 || E.o_first >= E.G.n_oct) return hipErrorInvalidValue;
+  const int rows = (E.G.row_off[E.G.n_oct] - E.G.row_off[E.o_first]) * std::max(1, P.nimg);
   hipLaunchKernelGGL(k_emit, dim3(std::max(1, (rows + 3) / 4)), dim3(256), 0, st, P, E);
   return hipGetLastError();
 }

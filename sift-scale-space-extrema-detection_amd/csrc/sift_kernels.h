@@ -68,19 +68,34 @@ constexpr int kXRows = SIFT_XROWS;  // centre rows per extrema wave (multiple of
 #endif
 constexpr int kXMaxGroup = SIFT_XMAXGROUP;// scales per extrema wave (S > 5 splits the scales into groups)
 
+// Geometry of the candidate bitmap and its row counts, built once per extrema
+// stage and carried by value in every launch struct that addresses them.
+// Octave o holds [S][h] rows of nw[o] words: rows row_off[o] .., words
+// word_off[o] ..; bit b of word xw of a row <-> column xw ww[o] + woff[o] + b.
+// Octaves decided by the scan have kXW-column words from column 0, octaves
+// decided in the Gaussian pass (FusedExtrema) kFX-column words from column 1.
+// A batch (P.nimg images) repeats the rows and words image-major.
+struct BitmapGeom {
+  int n_oct;
+  int row_off[kMaxOctaves + 1];     // first row of each octave; [n_oct] = rows per image
+  long long word_off[kMaxOctaves];  // first bitmap word of each octave
+  int nw[kMaxOctaves];              // words per row
+  int ww[kMaxOctaves];              // columns per word
+  int woff[kMaxOctaves];            // column of bit 0 of word 0
+  long long words_per_img;
+  int rows_per_img;
+};
+
 // One launch scans every octave: unit u (one wave) = (octave, strip of kXRows
 // rows, 62-column word, scale group).
 struct ExtremaLaunch {
-  int n_oct;
   int u_begin, u_end;            // units of this launch (a range of octaves)
   int exact_planes;              // DoG planes are the data itself (caller-supplied): no fp32 ties
   int ng;                        // scale groups per (strip, word)
   int xcd_band;                  // 1: block -> units so that each XCD scans a contiguous range of units
   float c_lo, c_hi;              // |v| < c_lo: certainly low contrast; |v| >= c_hi: certainly not
   int unit_off[kMaxOctaves + 1]; // first unit of each octave
-  int nw[kMaxOctaves];           // words per row
-  long long word_off[kMaxOctaves];  // first bitmap word of each octave ([S][h][nw])
-  int row_off[kMaxOctaves];      // first row count of each octave ([S][h])
+  BitmapGeom G;                  // of bitmap, rowcount, lowbitmap, lowrowcount, ambbitmap
   unsigned long long* bitmap;
   unsigned* rowcount;
   unsigned* amb_keys;            // keys needing an exact fp64 decision (unordered)
@@ -88,8 +103,6 @@ struct ExtremaLaunch {
   unsigned amb_cap;
   unsigned long long* lowbitmap; // certain low-contrast extrema, same layout as bitmap (nullptr = not listed)
   unsigned* lowrowcount;
-  long long words_per_img;       // batch (P.nimg images): image b's words / rows start b * these after image 0's
-  int rows_per_img;
   // Ambiguous words (ambbitmap != nullptr): instead of one key per ambiguous
   // pixel, the scan writes the word's ambiguous bits to ambbitmap (same
   // layout as bitmap) and lists the word's index (into bitmap) in amb_keys
@@ -98,16 +111,11 @@ struct ExtremaLaunch {
 };
 constexpr int kAmbWords = 8;     // counters slot: listed ambiguous words
 
-// One launch over every octave: global row g (one wave each) = row_off[o] +
+// One launch over every octave: global row g (one wave each) = G.row_off[o] +
 // (s-1) h_o + y.
 struct EmitLaunch {
-  int n_oct;
+  BitmapGeom G;
   int o_first;                   // first octave with decisions (earlier octaves' rows hold none: no waves)
-  int row_off[kMaxOctaves + 1];  // first global row of each octave ([S][h] rows per octave)
-  long long word_off[kMaxOctaves];  // first bitmap word of each octave
-  int nw[kMaxOctaves];
-  int ww[kMaxOctaves];           // columns per bitmap word: kXW (scan) or kFX (fused)
-  int woff[kMaxOctaves];         // column of bit 0 of word 0: 0 (scan) or 1 (fused)
   const unsigned long long* bitmap;
   const unsigned* rowcount;      // [all rows]
   const unsigned* rowoff;        // exclusive scan of rowcount
@@ -118,7 +126,6 @@ struct EmitLaunch {
   int deferred;                  // 1: value = NaN ("the fp32 plane value"): the refinement reads it from the
                                  // DoG plane (the centre of the 3x3x3 neighbourhood it gathers anyway),
                                  // launch_fill_values before the list is copied out; no plane gather here
-  long long words_per_img;       // batch: bitmap words per image (rows per image = row_off[n_oct])
   unsigned* n_out;               // != nullptr: *n_out = rowoff[n_index] (the list's length), by thread 0
   long long n_index;
 };
@@ -138,16 +145,11 @@ struct ExactLaunch {
   unsigned* counters;            // [6]: late low-contrast extrema (ambiguous ones decided low)
   unsigned* late_keys;           // their keys / exact values (nullptr = not listed), amb_cap slots
   double* late_vals;
-  // Emission geometry (EmitLaunch): a key's list position is its row's offset
-  // plus the candidate bits before it in the row's bitmap words (bitmap ==
-  // nullptr: binary search over keys).
+  // A key's list position is its row's offset plus the candidate bits before
+  // it in the row's bitmap words (bitmap == nullptr: binary search over keys).
   const unsigned long long* bitmap;
   const unsigned* rowoff;
-  int row_off[kMaxOctaves];
-  long long word_off[kMaxOctaves];
-  int nw[kMaxOctaves], ww[kMaxOctaves], woff[kMaxOctaves];
-  long long words_per_img;       // batch: bitmap words / rows per image
-  int rows_per_img;
+  BitmapGeom G;
   const unsigned long long* ambbitmap;  // ambiguous words (k_exact_words; nullptr: amb_keys are pixel keys)
   int amb_lds_stride;            // k_exact_words: doubles per vertical-sum row (64 + 2 rmax)
   int amb_patch_stride;          // ... doubles per wave of the per-pixel patch scratch
@@ -179,16 +181,15 @@ struct RefineLaunch {
 #endif
 constexpr int kBandRows = SIFT_BAND_ROWS;
 struct BandOrder {
-  int n_oct, S, n_items;
+  BitmapGeom G;                   // rows of rowoff: global row (o, s = 1, y = 0) = G.row_off[o]
+  int S, n_items;
   int item_off[kMaxOctaves + 1];  // first item of each octave: items (band, scale) of octave o
-  int row_off[kMaxOctaves + 1];   // first global row (o, s = 1, y = 0) of each octave in rowoff
   const unsigned* rowoff;         // exclusive scan of the extrema stage's row counts
   unsigned* count;                // per item: slots in it
   unsigned* first;                // per item: its first slot
   const unsigned* start;          // per item: exclusive scan of count (first position in the new order)
   unsigned* perm;                 // out: position -> slot
-  int cap;
-  int rows_per_img;               // batch: rowoff rows per image (items are image-major, item_off per image)
+  int cap;                        // (a batch: items are image-major, item_off per image)
 };
 hipError_t launch_band_items(const Pyramid& P, const BandOrder& B, hipStream_t st);
 hipError_t launch_band_fill(const Pyramid& P, const BandOrder& B, hipStream_t st);
@@ -228,8 +229,9 @@ bool gauss_vsplit(const Pyramid& P, int o);
 bool gauss_wide(const Pyramid& P, int o);
 // The octave-1 base straight from the input (bit-identical to the octave-0 launch's seeds).
 
-// Fills the unit table of L (octave geometry) and launches the scan; returns
-// the launch error.  L.bitmap words per octave: S * h * nw.
+// Fills the unit table of L and launches the scan; returns the launch error.
+// The octaves [o_begin, o_end) of L.G must have the scan's word geometry
+// (extrema_words_per_row words of kXW columns), else hipErrorInvalidValue.
 hipError_t launch_extrema(const Pyramid& P, ExtremaLaunch& L, hipStream_t st, int o_begin, int o_end);
 inline int extrema_words_per_row(int w) { return (w + kXW - 1) / kXW; }
 hipError_t launch_emit(const Pyramid& P, const EmitLaunch& E, hipStream_t st);

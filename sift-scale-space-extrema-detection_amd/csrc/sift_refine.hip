@@ -468,15 +468,15 @@ hipError_t launch_fill_values(const Pyramid& P, const unsigned* keys, double* va
 __global__ __launch_bounds__(256) void k_band_items(const Pyramid P, const BandOrder B) {
   const int it = blockIdx.x * 256 + threadIdx.x;
   if (it >= B.n_items) return;
-  const int ipi = B.item_off[B.n_oct];  // items per image (image-major)
+  const int ipi = B.item_off[B.G.n_oct];  // items per image (image-major)
   const int im = it / ipi, il = it - im * ipi;
   int o = 0;
-  while (o + 1 < B.n_oct && il >= B.item_off[o + 1]) ++o;
+  while (o + 1 < B.G.n_oct && il >= B.item_off[o + 1]) ++o;
   const int loc = il - B.item_off[o];
   const int b = loc / B.S, s = loc % B.S + 1;
   const int h = P.oct[o].h;
   const int y0 = b * kBandRows, y1 = min(h, y0 + kBandRows);
-  const long long r0 = (long long)im * B.rows_per_img + B.row_off[o] + (s - 1) * h + y0;
+  const long long r0 = (long long)im * B.G.rows_per_img + B.G.row_off[o] + (s - 1) * h + y0;
   const unsigned f = B.rowoff[r0];
   B.first[it] = f;
   B.count[it] = B.rowoff[r0 + (y1 - y0)] - f;

@@ -203,6 +203,35 @@ def test_fused_extrema_flag_same_results(gpu_ctx, W, H, O, S, seed):
     assert na["low_contrast"] == nb["low_contrast"] and na["candidates"] == nb["candidates"]
 
 
+def test_fused_extrema_exact_keys_on_saturated_image(gpu_ctx):
+    """k_exact_extrema in key mode, list positions from the bitmap geometry,
+    with real work: fused octave-0 decisions list ambiguous pixel keys, and in
+    that one launch octave 0 has 60-column words from column 1 while octaves
+    1 and 2 have 62-column words from column 0.  The saturated image (clipped
+    share 0.486) has 2,544 input pixels whose 15x15 neighbourhood is constant;
+    each gives 4 octave-0 pixels x 3 scales of exactly-zero DoG: 30,528
+    guaranteed fp32 ties, all interior.  The plain detection runs first: it
+    grows the ambiguous-key capacity past the tie count, so the fused run does
+    not overflow and fall back to the unfused retry."""
+    W, H, O, S = 200, 150, 3, 3
+    img = blob_image(W, H, seed=1)
+    img = (np.clip(np.rint((img - 0.5) * 3.0 * 4096 + 2048), 0, 4096) / 4096).astype(np.float32)
+    assert (img == 0).mean() + (img == 1).mean() > 0.4
+    a = gpu_ctx.detect(img, sift_amd.make_params(O, S)).copy()
+    ca, na = gpu_ctx.candidates(), gpu_ctx.counts()
+    p = sift_amd.make_params(O, S, flags=sift_amd.F_FUSED_EXTREMA)
+    b = gpu_ctx.detect(img, p).copy()
+    cb, nb = gpu_ctx.candidates(), gpu_ctx.counts()
+    print("\nsaturated %dx%d O%d S%d: %d candidates, %d keypoints, exact re-decisions plain %d, fused %d"
+          % (W, H, O, S, ca.shape[0], a.shape[0], na["exact"], nb["exact"]))
+    assert a.tobytes() == b.tobytes() and ca.tobytes() == cb.tobytes()
+    assert na["exact"] == nb["exact"]
+    assert na["exact"] >= 10000 and nb["exact"] >= 10000  # a third of the derived minimum: not a vacuous run
+    r = orc.OracleRun(img, oracle_params(p), orc.CONV_SEPARABLE_FMA_VH, threads=host_threads())
+    check_candidates(cb, r.candidates())
+    check_keypoints(b, r.refined)
+
+
 @pytest.mark.timeout(300)
 def test_capacity_growth_on_dense_extrema():
     """A fresh context starts from a geometry estimate of its candidate,
