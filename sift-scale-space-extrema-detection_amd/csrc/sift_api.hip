@@ -154,6 +154,7 @@ struct sift_ctx {
   std::vector<int> dims;           // 2*O
   std::vector<double> blur, sigma; // O*NS
   Pyramid P{};
+  GaussPlan gplan[kMaxOctaves]{};  // of P's octaves (setup_geometry)
   int dog_source = kNone;
   bool have_gauss = false;
   bool have_cand = false;
@@ -549,10 +550,12 @@ static int setup_geometry(sift_ctx* ctx, int W, int H, const sift_params* p, con
   }
   P.nimg = 1;  // one image (build_common sets a batch)
   P.kpi = (unsigned)koff;
-  // LDS feasibility of the Gaussian kernel (two strips of 32 rows x (76 + 2R) fp64).
-  for (int o = 0; o < O; ++o)
-    if (gauss_lds_bytes(P, o) > 160 * 1024)
+  // Every octave's Gaussian launch; its strip (32 rows x (76 + 2R) fp64) must fit the LDS.
+  for (int o = 0; o < O; ++o) {
+    ctx->gplan[o] = gauss_plan(P, o);
+    if (ctx->gplan[o].lds > kGaussMaxLds)
       return set_err(ctx, SIFT_E_UNSUPPORTED, "blur radius too large for one LDS strip");
+  }
   if (need_weights) {
     // Upload only when the taps changed (the same schedule image after image).
     // The taps are laid out octave after octave, so a schedule with fewer
@@ -609,6 +612,8 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
   int rc = setup_geometry(ctx, W, H, p, sig, true);
   if (rc) return rc;
   Pyramid& P = ctx->P;
+  const GaussPlan* const plan = ctx->gplan;
+  const bool needs_base0 = plan[0].path == kGaussBase0;
   if (o_first < 0 || o_first >= P.O) return set_err(ctx, SIFT_E_ARG, "octave_first out of range");
   ctx->o_first = o_first;
   ctx->scan_first = o_first;
@@ -622,7 +627,7 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
   const long long tot = total_plane_px(ctx);
   const bool keep_gauss = !(p->flags & SIFT_F_SKIP_GAUSS_PLANES);
   if (nimg > 1) {
-    if (o_first != 0 || (!img_host && !img_dev) || fuse_extrema || gauss_needs_base0(P) || ctx->row0 != 0 ||
+    if (o_first != 0 || (!img_host && !img_dev) || fuse_extrema || needs_base0 || ctx->row0 != 0 ||
         ctx->own_lo >= 0 ||
         (p->flags & (SIFT_F_EXPORT_NEXT_SEED | SIFT_F_LOW_CONTRAST_LIST | SIFT_F_FUSED_EXTREMA |
                      SIFT_F_KEYPOINT_ORIGINS)))  // origins carry no image index
@@ -690,7 +695,7 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
   {  // large-radius octaves keep their fp64 Gaussian planes (the exact passes read them)
     long long l64 = 0;
     for (int o = so_end; o < P.O; ++o)
-      if (gauss_keep_l64(P, o)) {
+      if (plan[o].keep_l64) {
         P.oct[o].l64_off = l64;
         l64 += (long long)P.NS * P.oct[o].h * P.oct[o].w;
       }
@@ -699,7 +704,7 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
     P.l64_bstride = l64;
     size_t vs = 0;  // the split-pass octaves run in turn on this stream: one scratch (per image)
     for (int o = so_end; o < P.O; ++o)
-      if (gauss_vsplit(P, o)) vs = std::max(vs, (size_t)P.NS * P.oct[o].h * P.oct[o].w);
+      if (plan[o].vsplit) vs = std::max(vs, (size_t)P.NS * P.oct[o].h * P.oct[o].w);
     size_t sv = 0;
     for (int o = o_first; o < so_end; ++o) sv = std::max(sv, seed_only_scratch(P, o));
     if (sv) HIPCHK(ctx->seedv.ensure(sv * sizeof(double)));
@@ -708,7 +713,7 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
     // after the pass the scratch holds the last split octave's sums (octaves run in order)
     P.vsum_oct = -1;
     for (int o = so_end; o < P.O; ++o)
-      if (gauss_vsplit(P, o)) P.vsum_oct = o;
+      if (plan[o].vsplit) P.vsum_oct = o;
     static const int vsum_exact = exp_knob("SIFT_VSUM_EXACT", 1);  // 0: the exact passes recompute (A/B)
     if (!vsum_exact) P.vsum_oct = -1;
     P.vsum = P.vsum_oct >= 0 ? ctx->vsplit.as<double>() : nullptr;
@@ -716,13 +721,13 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
   }
   HIPCHK(hipEventRecord(ctx->ev[1], ctx->stream));
   const double* base0 = nullptr;
-  if (o_first == 0 && gauss_needs_base0(P)) {
+  if (o_first == 0 && needs_base0) {
     HIPCHK(ctx->base0.ensure((size_t)P.oct[0].h * P.oct[0].w * sizeof(double)));
     HIPCHK(launch_upsample_base(P, ctx->base0.as<double>(), ctx->stream));
     base0 = ctx->base0.as<double>();
   }
   ctx->x_prepared = false;
-  const int nf = (fuse_extrema && o_first == 0 && fuse_enabled(p) && gauss_can_fuse(P, 0) &&
+  const int nf = (fuse_extrema && o_first == 0 && fuse_enabled(p) && plan[0].can_fuse &&
                   !(p->flags & SIFT_F_LOW_CONTRAST_LIST)) ? 1 : 0;
   if (nf) {  // bitmap geometry, counter resets: before the fused launch writes them
     ctx->dog_source = kNative;
@@ -769,7 +774,7 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
       L.X.c_hi = XL.c_hi;
     }
     L.l64 = P.oct[o].l64_off >= 0 ? ctx->l64.as<double>() + P.oct[o].l64_off : nullptr;
-    L.vsplit = gauss_vsplit(P, o) ? ctx->vsplit.as<double>() : nullptr;
+    L.vsplit = plan[o].vsplit ? ctx->vsplit.as<double>() : nullptr;
     L.nimg = nimg;
     L.gauss_bs = tot * P.NS;
     L.dog_bs = tot * P.ND;
@@ -777,9 +782,8 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
     L.base_bs = o == 0 ? 0 : seeds_pi;
     L.l64_bs = P.l64_bstride;
     L.vsplit_bs = ctx->vsplit_pi;
-    const char* kn = nullptr;
-    HIPCHK(launch_gauss_dog(P, L, ost, 0, -1, &kn));
-    ctx->pass_kn[o] = std::string(o == 0 && base0 ? "k_upsample_base + " : "") + (kn ? kn : "?");
+    HIPCHK(launch_gauss_dog(P, plan[o], L, ost));
+    ctx->pass_kn[o] = L.fuse ? kGaussFusedName : plan[o].kname;
     if (o == o_first) HIPCHK(hipEventRecord(ctx->ev[7], ost));
     HIPCHK(hipEventRecord(ctx->ev_go[o], ost));
   }

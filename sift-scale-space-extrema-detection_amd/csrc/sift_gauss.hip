@@ -67,25 +67,17 @@ constexpr int kUR = 16;              // radii with unrolled code (octave 0)
 #ifndef SIFT_MINW1
 #define SIFT_MINW1 1
 #endif
-#ifndef SIFT_W96
-#define SIFT_W96 1  // 96-column kernel: minimum waves per SIMD (register budget; experiments)
-#endif
-#ifndef SIFT_TW96_SEQ
-#define SIFT_TW96_SEQ 2  // 96-column kernel: horizontal items 0-1 side by side then 2, each group with its epilogue
-                         // (122 VGPRs, 4 waves/SIMD; 1 = one at a time, 0 = all three interleaved, 138 VGPRs)
-#endif
-#ifndef SIFT_PF96
-#define SIFT_PF96 2
-#endif
 #ifndef SIFT_V2PF
 #define SIFT_V2PF 4  // 16-byte rows in flight in vert_glob2 (4 and 6 measured equal; 4: 108 VGPRs)
 #endif
 constexpr int kUR1 = SIFT_UR1;       // ... octaves >= 1 (SGPR budget: taps are SGPR operands)
-constexpr int kUR96 = kUR1 < 12 ? kUR1 : 12;  // ... 96-column tiles (96 + 2r columns in 64 lanes x 2)
 constexpr int kCG = kGX / 4;         // column groups of 4 outputs (16)
 constexpr int kRS = 64 / kCG;        // row sub-groups per wave (4)
 constexpr int kNR = 8 / kRS;         // rows per lane in the horizontal pass (2)
 constexpr int kBW0 = kGX / 2 + kUR + 4;  // staged octave-0 region width (input columns)
+constexpr int kSW0 = 2 * (kCG - 1) + 8 + 6;    // octave-0 strip stride for rmax <= 8
+constexpr int kSW1 = 2 * (kCG - 1) + kUR + 6;  // ... rmax <= kUR
+static_assert(kGY == kFY + 2 && kGX >= kFX + 2, "a fused tile decides the pixels one in from its 64 x 32 origin");
 constexpr int kPFV = 12;             // rows in flight, vertical pass from global memory
 constexpr int kPFL = 4;              // rows in flight, vertical pass from LDS
 constexpr int kPFH = 3;              // 16-byte reads in flight, horizontal pass
@@ -102,7 +94,6 @@ struct GTile {
   int bx;              // tile column
   int lane, wv;        // wv wave-uniform (SGPR)
   int cg, rs;          // horizontal mapping (64-column tiles)
-  int icg[4], irow[4]; // 96- / 128-column tiles: item i of the lane = columns 4 icg .. +3 of wave row irow
   int sw;              // strip stride
   int hrm;             // octave 0: ceil(RM / 2) of the staged region
   const double* S0;    // octave 0: staged input region [..][kBW0]
@@ -263,9 +254,9 @@ __device__ __forceinline__ void vert_glob(const GTile& T, const cdouble* wp, dou
 // Column clamping: the pair (x, x+1) is read at xa = clamp(x, 0, w - 2); at
 // the left edge both columns are B[0] (the pair's first), at the right edge
 // both are B[w-1] (its second).  Same fma chain per column, bit-identical.
-template <int R, int TW = kGX>
+template <int R>
 __device__ __forceinline__ void vert_glob2(const GTile& T, const cdouble* wp, double* V) {
-  constexpr int NC = TW + 2 * R;  // even
+  constexpr int NC = kGX + 2 * R;  // even
   constexpr int NPAIR = NC / 2;
   static_assert(NPAIR <= 64, "one lane per column pair");
   constexpr int NJ = 2 * R + 8;
@@ -305,9 +296,9 @@ __device__ __forceinline__ void vert_glob2(const GTile& T, const cdouble* wp, do
     yy += 1;
     return __builtin_bit_cast(double2, q);
   };
-  // Tiles whose strip columns x0 - R .. x0 + TW + R - 1 all lie inside the
+  // Tiles whose strip columns x0 - R .. x0 + 63 + R all lie inside the
   // plane (wave-uniform) need no edge selects (4 VALU per 16-byte row).
-  if (T.x0 - R >= 0 && T.x0 + TW + R <= T.w) {
+  if (T.x0 - R >= 0 && T.x0 + kGX + R <= T.w) {
     run(raw);
   } else {
     const bool lo_edge = x < 0, hi_edge = x >= T.w - 1;
@@ -480,7 +471,7 @@ __device__ __forceinline__ void vert_glob_gen(const GTile& T, int r, const cdoub
 }
 
 // ---------------------------------------------------------------------------
-// Split vertical pass (large radii, gauss_vsplit).  A 64-column tile
+// Split vertical pass (large radii, kGaussSplitTiles).  A 64-column tile
 // recomputes the vertical sums of its 2r halo columns: (64 + 2r) / 64 of the
 // vertical work (2.5x at r = 47, 6.9x at r = 188), serialised in the tile's
 // waves.  k_gauss_vert computes every (scale, row, column) sum once, one lane
@@ -636,105 +627,6 @@ __device__ __forceinline__ void horz_full(const GTile& T, const cdouble* wp, con
   }
 }
 
-// 96-column tiles (octaves >= 1 whose radii are all unrolled): 24 column
-// groups x 8 rows = 192 items of 4 columns x 1 row, three per lane (item i =
-// lane + 64 i), so the 64 + 2r-column vertical pass of a 64-wide tile becomes
-// a 96 + 2r one with (96 + 2r) / 128 instead of (64 + 2r) / 128 of its lanes
-// busy and a third fewer loads per output.  Same fma chain per output.
-template <int R>
-__device__ __forceinline__ void horz_full96(const GTile& T, const cdouble* wp, const double* V, double (&out)[3][4]) {
-  constexpr int NP = R + 2;  // double2 pairs per row
-  constexpr int PF96 = SIFT_PF96;  // 16-byte reads in flight per item
-  const double* rp[3];
-  double2 u[3][NP];
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-    rp[i] = V + (8 * T.wv + T.irow[i]) * T.sw + 4 * T.icg[i];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[i][q] = 0.0;
-  }
-#pragma unroll
-  for (int n2 = 0; n2 < PF96 && n2 < NP; ++n2)
-#pragma unroll
-    for (int i = 0; i < 3; ++i) u[i][n2] = *reinterpret_cast<const double2*>(rp[i] + 2 * n2);
-#pragma unroll
-  for (int n2 = 0; n2 < NP; ++n2) {
-    if (n2 + PF96 < NP)
-#pragma unroll
-      for (int i = 0; i < 3; ++i) u[i][n2 + PF96] = *reinterpret_cast<const double2*>(rp[i] + 2 * (n2 + PF96));
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int n = 2 * n2 + e;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int k = n - q;
-        if (k >= 0 && k <= 2 * R)
-#pragma unroll
-          for (int i = 0; i < 3; ++i) out[i][q] = fma((double)wp[k], e ? u[i][n2].y : u[i][n2].x, out[i][q]);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pin(out[i]);
-  }
-}
-
-// The same, one item at a time, each handed to epi(i, out) as soon as its
-// 4 chains are done: only one item's accumulators and reads are live
-// (SIFT_TW96_SEQ; the interleaved form keeps all three).
-// Items [I0, I0 + NI) of the lane side by side (4 NI fma chains).
-template <int R, int I0, int NI, class Epi>
-__device__ __forceinline__ void horz96_group(const GTile& T, const cdouble* wp, const double* V, Epi&& epi) {
-  constexpr int NP = R + 2;  // double2 pairs per row
-  constexpr int PF = kPFH;
-  const double* rp[NI];
-  double out[NI][4];
-  double2 u[NI][NP];
-#pragma unroll
-  for (int j = 0; j < NI; ++j) {
-    rp[j] = V + (8 * T.wv + T.irow[I0 + j]) * T.sw + 4 * T.icg[I0 + j];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[j][q] = 0.0;
-  }
-#pragma unroll
-  for (int n2 = 0; n2 < PF && n2 < NP; ++n2)
-#pragma unroll
-    for (int j = 0; j < NI; ++j) u[j][n2] = *reinterpret_cast<const double2*>(rp[j] + 2 * n2);
-#pragma unroll
-  for (int n2 = 0; n2 < NP; ++n2) {
-    if (n2 + PF < NP)
-#pragma unroll
-      for (int j = 0; j < NI; ++j) u[j][n2 + PF] = *reinterpret_cast<const double2*>(rp[j] + 2 * (n2 + PF));
-#pragma unroll
-    for (int e = 0; e < 2; ++e) {
-      const int n = 2 * n2 + e;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int k = n - q;
-        if (k >= 0 && k <= 2 * R)
-#pragma unroll
-          for (int j = 0; j < NI; ++j) out[j][q] = fma((double)wp[k], e ? u[j][n2].y : u[j][n2].x, out[j][q]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < NI; ++j) pin(out[j]);
-  }
-#pragma unroll
-  for (int j = 0; j < NI; ++j) epi(I0 + j, out[j]);
-}
-
-// SIFT_TW96_SEQ 1: items one at a time; 2: items 0-1 side by side, then 2.
-template <int R, class Epi>
-__device__ __forceinline__ void horz_full96_seq(const GTile& T, const cdouble* wp, const double* V, Epi&& epi) {
-  if constexpr (SIFT_TW96_SEQ == 2) {
-    horz96_group<R, 0, 2>(T, wp, V, epi);
-    horz96_group<R, 2, 1>(T, wp, V, epi);
-  } else {
-    horz96_group<R, 0, 1>(T, wp, V, epi);
-    horz96_group<R, 1, 1>(T, wp, V, epi);
-    horz96_group<R, 2, 1>(T, wp, V, epi);
-  }
-}
-
 __device__ __forceinline__ void horz_full_gen(const GTile& T, int r, const cdouble* wp, const double* V,
                                               double (&out)[kNR][4]) {
   const int NV = 2 * r + 4;
@@ -825,29 +717,21 @@ __device__ __forceinline__ void rdispatch(int r, F&& f) {
   }
 }
 
-#ifndef SIFT_BIN_STREAM
-#define SIFT_BIN_STREAM 1  // binary radius dispatch in the streamed k_gauss_rw<RW, true> too
-#endif
-#ifndef SIFT_BIN_TILE
-#define SIFT_BIN_TILE 1  // binary radius dispatch in the k_gauss_dog tile kernels of octaves >= 1
-#endif
 #ifndef SIFT_BIN_OCT0
-#define SIFT_BIN_OCT0 1  // ... and in octave 0's (bit 0: vertical pass, bit 1: horizontal: +13 VGPRs)
+#define SIFT_BIN_OCT0 1  // binary dispatch in octave 0's passes (bit 0: vertical, bit 1: horizontal: +13 VGPRs)
 #endif
 // Measured (r6f / r6g, profiles/r6g_radius_dispatch_ab.txt): 4K octave 1
 // (register window) 0.162 -> 0.149 ms, octave 2 (streamed) 0.095 -> 0.089 ms,
-// octave 3's tiles -2 us; octave 0 runs its vertical pass binary and keeps
-// the compare chain in its horizontal pass (binary in both takes it from 92
-// to 105 VGPRs, 5 -> 4 waves per SIMD: 0.364 -> 0.383 ms; bounded to 96 it
-// spills: 0.370 ms).  The streamed kernels run binary.
+// octave 3's tiles -2 us: octaves >= 1 dispatch binary everywhere.  Octave 0
+// runs its vertical pass binary and keeps the compare chain in its
+// horizontal pass (binary in both takes it from 92 to 105 VGPRs, 5 -> 4
+// waves per SIMD: 0.364 -> 0.383 ms; bounded to 96 it spills: 0.370 ms).
 template <bool OCT0, int... Rs>
 __device__ __forceinline__ void vert_any_(std::integer_sequence<int, Rs...>, const GTile& T, int r,
                                          const cdouble* wp, double* V) {
   constexpr int N = sizeof...(Rs) - 1;
-  if constexpr (OCT0 ? (SIFT_BIN_OCT0 & 1) : SIFT_BIN_TILE) {
-    if constexpr (OCT0) {
-      rdispatch<0, N>(r, [&](auto R) { vert_o0<decltype(R)::value>(T, wp, V); });
-    } else if (r <= N) {
+  if constexpr (!OCT0) {
+    if (r <= N) {
       if (T.w >= 2) rdispatch<0, N>(r, [&](auto R) { vert_glob2<decltype(R)::value>(T, wp, V); });
       else rdispatch<0, N>(r, [&](auto R) { vert_glob<decltype(R)::value>(T, wp, V); });
     } else if (T.w >= 2 && r <= 32) {
@@ -855,19 +739,11 @@ __device__ __forceinline__ void vert_any_(std::integer_sequence<int, Rs...>, con
     } else {
       vert_glob_gen(T, r, wp, V);
     }
-    return;
-  }
-  bool done = false;
-  if constexpr (OCT0) {
-    ((!done && r == Rs ? (vert_o0<Rs>(T, wp, V), done = true) : false), ...);
+  } else if constexpr (SIFT_BIN_OCT0 & 1) {
+    rdispatch<0, N>(r, [&](auto R) { vert_o0<decltype(R)::value>(T, wp, V); });
   } else {
-    if (T.w >= 2) {
-      ((!done && r == Rs ? (vert_glob2<Rs>(T, wp, V), done = true) : false), ...);
-      if (!done && r <= 32) vert_glob_gen2(T, r, wp, V), done = true;
-    } else {
-      ((!done && r == Rs ? (vert_glob<Rs>(T, wp, V), done = true) : false), ...);
-    }
-    if (!done) vert_glob_gen(T, r, wp, V);
+    bool done = false;
+    ((!done && r == Rs ? (vert_o0<Rs>(T, wp, V), done = true) : false), ...);
   }
 }
 
@@ -875,55 +751,15 @@ template <bool OCT0, int... Rs>
 __device__ __forceinline__ void horz_any_(std::integer_sequence<int, Rs...>, const GTile& T, int r,
                                          const cdouble* wp, const double* V, double (&out)[kNR][4]) {
   constexpr int N = sizeof...(Rs) - 1;
-  if constexpr (OCT0 ? (SIFT_BIN_OCT0 & 2) : SIFT_BIN_TILE) {
-    if constexpr (OCT0) {
-      rdispatch<0, N>(r, [&](auto R) { horz_o0<decltype(R)::value>(T, wp, V, out); });
-    } else if (r <= N) {
-      rdispatch<0, N>(r, [&](auto R) { horz_full<decltype(R)::value>(T, wp, V, out); });
-    } else {
-      horz_full_gen(T, r, wp, V, out);
-    }
-    return;
-  }
-  bool done = false;
-  if constexpr (OCT0) {
-    ((!done && r == Rs ? (horz_o0<Rs>(T, wp, V, out), done = true) : false), ...);
+  if constexpr (!OCT0) {
+    if (r <= N) rdispatch<0, N>(r, [&](auto R) { horz_full<decltype(R)::value>(T, wp, V, out); });
+    else horz_full_gen(T, r, wp, V, out);
+  } else if constexpr (SIFT_BIN_OCT0 & 2) {
+    rdispatch<0, N>(r, [&](auto R) { horz_o0<decltype(R)::value>(T, wp, V, out); });
   } else {
-    ((!done && r == Rs ? (horz_full<Rs>(T, wp, V, out), done = true) : false), ...);
-    if (!done) horz_full_gen(T, r, wp, V, out);
+    bool done = false;
+    ((!done && r == Rs ? (horz_o0<Rs>(T, wp, V, out), done = true) : false), ...);
   }
-}
-
-template <int... Rs>
-__device__ __forceinline__ void vert96_any_(std::integer_sequence<int, Rs...>, const GTile& T, int r,
-                                           const cdouble* wp, double* V) {
-  if constexpr (SIFT_BIN_TILE) {
-    rdispatch<0, sizeof...(Rs) - 1>(r, [&](auto R) { vert_glob2<decltype(R)::value, 96>(T, wp, V); });
-    return;
-  }
-  bool done = false;
-  ((!done && r == Rs ? (vert_glob2<Rs, 96>(T, wp, V), done = true) : false), ...);
-}
-template <int... Rs>
-__device__ __forceinline__ void horz96_any_(std::integer_sequence<int, Rs...>, const GTile& T, int r,
-                                           const cdouble* wp, const double* V, double (&out)[3][4]) {
-  if constexpr (SIFT_BIN_TILE) {
-    rdispatch<0, sizeof...(Rs) - 1>(r, [&](auto R) { horz_full96<decltype(R)::value>(T, wp, V, out); });
-    return;
-  }
-  bool done = false;
-  ((!done && r == Rs ? (horz_full96<Rs>(T, wp, V, out), done = true) : false), ...);
-}
-
-template <class Epi, int... Rs>
-__device__ __forceinline__ void horz96s_any_(std::integer_sequence<int, Rs...>, const GTile& T, int r,
-                                            const cdouble* wp, const double* V, Epi&& epi) {
-  if constexpr (SIFT_BIN_TILE) {
-    rdispatch<0, sizeof...(Rs) - 1>(r, [&](auto R) { horz_full96_seq<decltype(R)::value>(T, wp, V, epi); });
-    return;
-  }
-  bool done = false;
-  ((!done && r == Rs ? (horz_full96_seq<Rs>(T, wp, V, epi), done = true) : false), ...);
 }
 
 // Unrolled radii 0..RMAX.
@@ -1032,9 +868,6 @@ __device__ __forceinline__ void fused_decide(const Pyramid& P, const GaussLaunch
 
 // SWC > 0: compile-time strip stride (immediate LDS offsets); 0: L.sw.
 // RMAX: radii with unrolled code.  XF: extrema decisions fused (above).
-// TW: tile width (64; 96 for octaves >= 1 whose radii are all unrolled,
-// horz_full96); NI items of 4 columns x 1 row per lane in the horizontal pass
-// and the epilogue.
 #ifndef SIFT_VS_RMAX
 #define SIFT_VS_RMAX 12  // ... with unrolled horizontal radii up to this
 #endif
@@ -1045,10 +878,8 @@ __device__ __forceinline__ void fused_decide(const Pyramid& P, const GaussLaunch
 // come from the split pass's vertical sums only, so the vertical radius
 // variants are not compiled into it (round 6: the shared instance spilled
 // 126 SGPRs into VGPR lanes, readlane / writelane in every scale).
-template <bool OCT0, int SWC, int RMAX, bool XF, int TW = kGX, bool VS = false>
-__global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : (TW == 96 ? SIFT_W96 : SIFT_MINW1)) void k_gauss_dog(const Pyramid P, const GaussLaunch L) {
-  static_assert(TW == kGX || (TW == 96 && !OCT0 && !XF && RMAX <= 16), "96-column tiles: octaves >= 1, unrolled radii");
-  constexpr int NI = TW == kGX ? kNR : 3;
+template <bool OCT0, int SWC, int RMAX, bool XF, bool VS = false>
+__global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : SIFT_MINW1) void k_gauss_dog(const Pyramid P, const GaussLaunch L) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const Octave& oc = P.oct[L.o];
   // 1D grid: block -> (scale group, tile).  Blocks are dispatched round-robin
@@ -1073,29 +904,17 @@ __global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : (TW == 96 ? SIFT_W96 : SIFT_M
   const double* const L_vsplit = L.vsplit ? L.vsplit + im * L.vsplit_bs : nullptr;
   const float* const img_b = OCT0 ? P.img + im * P.img_bstride : nullptr;
   const int bz = lb % L.G, bt = lb / L.G;
-  const int bx = bt % L.gx, by = bt / L.gx + L.by0;
+  const int bx = bt % L.gx, by = bt / L.gx;
   GTile T;
   T.bx = bx;
   T.h = oc.h;
   T.w = oc.w;
-  T.x0 = bx * (XF ? kFX : TW);
+  T.x0 = bx * (XF ? kFX : kGX);
   T.y0 = by * (XF ? kFY : kGY);
   T.lane = threadIdx.x & 63;
   T.wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   T.cg = T.lane & (kCG - 1);
   T.rs = T.lane / kCG;
-  if constexpr (TW == 96) {
-    int g, j;  // conflict-free ds_read_b128 item map
-    b128_group(T.lane, g, j);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      T.icg[i] = 8 * i + (j & 7);
-      T.irow[i] = 2 * g + (j >> 3);
-    }
-  }
-  // item i of the lane: wave row irw(i), first column x0 + 4 icg(i)
-  auto irw = [&](int i) { return TW == kGX ? T.rs + kRS * i : T.irow[i]; };
-  auto icg = [&](int i) { return TW == kGX ? T.cg : T.icg[i]; };
   T.sw = SWC > 0 ? SWC : L.sw;
   T.hrm = cl2(oc.rmax);
   if (!OCT0)
@@ -1131,16 +950,16 @@ __global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : (TW == 96 ? SIFT_W96 : SIFT_M
   const long long plane = (long long)T.h * T.w;
   // Pixels this block stores: all of its tile, or with fused extrema the
   // kFX x kFY it owns (the last tile of a row / column: all it computes).
-  bool own[NI];
+  bool own[kNR];
   // Per-lane byte offsets of its output items in a plane (past the plane or
   // not owned: the store is dropped).
-  int voff[NI];
+  int voff[kNR];
 #pragma unroll
-  for (int i = 0; i < NI; ++i) {
-    const int r = 8 * T.wv + irw(i);
+  for (int i = 0; i < kNR; ++i) {
+    const int r = 8 * T.wv + T.rs + kRS * i;
     const int y = T.y0 + r;
-    const int x = T.x0 + 4 * icg(i);
-    const bool own_c = !XF || 4 * icg(i) < kFX || bx == L.gx - 1;
+    const int x = T.x0 + 4 * T.cg;
+    const bool own_c = !XF || 4 * T.cg < kFX || bx == L.gx - 1;
     own[i] = y < T.h && T.w - x > 0 && own_c && (!XF || r < kFY || by == L.gy - 1);
     voff[i] = own[i] ? (y * T.w + x) * 4 : 0x7ffffff0;
   }
@@ -1152,8 +971,7 @@ __global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : (TW == 96 ? SIFT_W96 : SIFT_M
   const int s_first = max(0, s_begin - 1);
   __syncthreads();  // staged region / zeroed strip visible to every wave
 
-  const bool st = !(L.dbg & 1);  // dbg 1: timing without plane stores
-  double lprev[NI][4];
+  double lprev[kNR][4];
   for (int s = s_first; s < s_end; ++s) {
     const cdouble* wp = (const cdouble*)(P.wts + oc.wofs[s]);
     // Per-lane indices made opaque each scale: otherwise the compiler hoists
@@ -1161,86 +979,42 @@ __global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : (TW == 96 ? SIFT_W96 : SIFT_M
     // keeps it all live (dozens of VGPRs, half the occupancy).
     GTile Ts = T;
     asm volatile("" : "+v"(Ts.lane), "+v"(Ts.cg), "+v"(Ts.rs));
-    if constexpr (TW == 96 && SIFT_TW96_SEQ) {
-      // one item at a time: horizontal chains, then its stores, DoG and seed
-      vert96_any_(std::make_integer_sequence<int, RMAX + 1>{}, Ts, oc.rad[s], wp, V);
-      wave_lds_fence();  // this wave's strip rows written -> read by its other lanes
-      const unsigned pb = (unsigned)plane * 4u;
-      const bool stor = s >= s_begin && st;
-      const __amdgpu_buffer_rsrc_t rg =
-          urs(L_gauss ? L_gauss + s * plane : L_dog, pb);
-      const __amdgpu_buffer_rsrc_t rd =
-          urs(L_dog + (s > 0 ? s - 1 : 0) * plane, pb);
-      horz96s_any_(std::make_integer_sequence<int, RMAX + 1>{}, Ts, oc.rad[s], wp, V,
-                   [&](int i, const double (&o)[4]) {
-                     double d[4];
-#pragma unroll
-                     for (int q = 0; q < 4; ++q) d[q] = lprev[i][q] - o[q];
-                     const int y = T.y0 + 8 * T.wv + irw(i);
-                     const int x = T.x0 + 4 * icg(i), nvalid = T.w - x;
-                     if (stor) {
-                       if (L.vec) {
-                         if (L_gauss) bstore4(rg, voff[i], o);
-                         if (s > 0) bstore4(rd, voff[i], d);
-                       } else if (own[i]) {
-                         const long long pp = (long long)y * T.w + x;
-                         if (L_gauss) store4(L_gauss + s * plane + pp, o, nvalid);
-                         if (s > 0) store4(L_dog + (s - 1) * plane + pp, d, nvalid);
-                       }
-                     }
-                     if (s == P.S && L_next_seed && s >= s_begin && own[i] && !(y & 1)) {
-                       double* sd = L_next_seed + (long long)(y >> 1) * L.next_w + (x >> 1);
-                       sd[0] = o[0];
-                       if (nvalid > 2) sd[1] = o[2];
-                     }
-#pragma unroll
-                     for (int q = 0; q < 4; ++q) lprev[i][q] = o[q];
-                   });
-      wave_lds_fence();  // strip rows read before the next scale overwrites them
-      continue;
-    }
-    double out[NI][4];
-    if constexpr (TW == 96) {
-      vert96_any_(std::make_integer_sequence<int, RMAX + 1>{}, Ts, oc.rad[s], wp, V);
-      wave_lds_fence();  // this wave's strip rows written -> read by its other lanes
-      horz96_any_(std::make_integer_sequence<int, RMAX + 1>{}, Ts, oc.rad[s], wp, V, out);
+    double out[kNR][4];
+    if constexpr (VS) {
+      vert_copy(Ts, oc.rad[s], L_vsplit + (long long)s * plane, V);
+    } else if constexpr (!OCT0) {
+      if (L_vsplit) vert_copy(Ts, oc.rad[s], L_vsplit + (long long)s * plane, V);
+      else vert_any<OCT0, RMAX>(Ts, oc.rad[s], wp, V);
     } else {
-      if constexpr (VS) {
-        vert_copy(Ts, oc.rad[s], L_vsplit + (long long)s * plane, V);
-      } else if constexpr (!OCT0) {
-        if (L_vsplit) vert_copy(Ts, oc.rad[s], L_vsplit + (long long)s * plane, V);
-        else vert_any<OCT0, RMAX>(Ts, oc.rad[s], wp, V);
-      } else {
-        vert_any<OCT0, RMAX>(Ts, oc.rad[s], wp, V);
-      }
-      wave_lds_fence();  // this wave's strip rows written -> read by its other lanes
-      horz_any<OCT0, RMAX>(Ts, oc.rad[s], wp, V, out);
+      vert_any<OCT0, RMAX>(Ts, oc.rad[s], wp, V);
     }
+    wave_lds_fence();  // this wave's strip rows written -> read by its other lanes
+    horz_any<OCT0, RMAX>(Ts, oc.rad[s], wp, V, out);
     wave_lds_fence();  // strip rows read before the next scale overwrites them
 
-    double d[NI][4];
+    double d[kNR][4];
 #pragma unroll
-    for (int i = 0; i < NI; ++i)
+    for (int i = 0; i < kNR; ++i)
 #pragma unroll
       for (int q = 0; q < 4; ++q) d[i][q] = lprev[i][q] - out[i][q];
-    if (s >= s_begin && (st || out[0][0] == 12345.0)) {
+    if (s >= s_begin) {
       if (L.vec) {
         const unsigned pb = (unsigned)plane * 4u;
         if (L_gauss) {
           const __amdgpu_buffer_rsrc_t rg = urs(L_gauss + s * plane, pb);
 #pragma unroll
-          for (int i = 0; i < NI; ++i) bstore4(rg, voff[i], out[i]);
+          for (int i = 0; i < kNR; ++i) bstore4(rg, voff[i], out[i]);
         }
         if (s > 0) {
           const __amdgpu_buffer_rsrc_t rd = urs(L_dog + (s - 1) * plane, pb);
 #pragma unroll
-          for (int i = 0; i < NI; ++i) bstore4(rd, voff[i], d[i]);
+          for (int i = 0; i < kNR; ++i) bstore4(rd, voff[i], d[i]);
         }
       } else {
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-          const int y = T.y0 + 8 * T.wv + irw(i);
-          const int x = T.x0 + 4 * icg(i), nvalid = T.w - x;
+        for (int i = 0; i < kNR; ++i) {
+          const int y = T.y0 + 8 * T.wv + T.rs + kRS * i;
+          const int x = T.x0 + 4 * T.cg, nvalid = T.w - x;
           if (own[i]) {
             const long long pp = (long long)y * T.w + x;
             if (L_gauss) store4(L_gauss + s * plane + pp, out[i], nvalid);
@@ -1262,16 +1036,16 @@ __global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : (TW == 96 ? SIFT_W96 : SIFT_M
         }
         if (s >= 3) {
           lds_barrier();  // every wave's rows of DoG s-1 are in the ring
-          if (!(L.dbg & 2)) fused_decide(P, L, Ts, ring, s - 2, xlow);  // dbg 2: timing without the decisions
+          fused_decide(P, L, Ts, ring, s - 2, xlow);
         }
       }
     }
     if (L_l64 && s >= s_begin) {  // fp64 plane for the exact passes
       double* lp = L_l64 + s * plane;
 #pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const int y = T.y0 + 8 * T.wv + irw(i);
-        const int x = T.x0 + 4 * icg(i), nvalid = T.w - x;
+      for (int i = 0; i < kNR; ++i) {
+        const int y = T.y0 + 8 * T.wv + T.rs + kRS * i;
+        const int x = T.x0 + 4 * T.cg, nvalid = T.w - x;
         if (own[i]) {
 #pragma unroll
           for (int q = 0; q < 4; ++q)
@@ -1281,9 +1055,9 @@ __global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : (TW == 96 ? SIFT_W96 : SIFT_M
     }
     if (s == P.S && L_next_seed && s >= s_begin) {
 #pragma unroll
-      for (int i = 0; i < NI; ++i) {
-        const int y = T.y0 + 8 * T.wv + irw(i);
-        const int x = T.x0 + 4 * icg(i), nvalid = T.w - x;
+      for (int i = 0; i < kNR; ++i) {
+        const int y = T.y0 + 8 * T.wv + T.rs + kRS * i;
+        const int x = T.x0 + 4 * T.cg, nvalid = T.w - x;
         if (own[i] && !(y & 1)) {
           double* sd = L_next_seed + (long long)(y >> 1) * L.next_w + (x >> 1);
           sd[0] = out[i][0];
@@ -1292,7 +1066,7 @@ __global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : (TW == 96 ? SIFT_W96 : SIFT_M
       }
     }
 #pragma unroll
-    for (int i = 0; i < NI; ++i)
+    for (int i = 0; i < kNR; ++i)
 #pragma unroll
       for (int q = 0; q < 4; ++q) lprev[i][q] = out[i][q];
   }
@@ -1345,7 +1119,7 @@ __host__ __device__ constexpr int rw_row(int t) { return t * kRwSW + 2 * (t >> 2
 #define SIFT_RWTAPS 8  // taps per reload of the tap pointer (0: never: the compiler keeps them in SGPRs)
 #endif
 #ifndef SIFT_RWS_DEFAULT
-#define SIFT_RWS_DEFAULT 1  // streamed k_gauss_rw for radii 13..24 (gauss_rws; profiles/r5k_streamed_rw_ab.txt)
+#define SIFT_RWS_DEFAULT 1  // streamed k_gauss_rw for radii 13..24 (gauss_plan; profiles/r5k_streamed_rw_ab.txt)
 #endif
 #ifndef SIFT_RW_WPE
 #define SIFT_RW_WPE 1  // minimum waves per SIMD the register allocation must allow
@@ -1428,17 +1202,10 @@ __device__ __forceinline__ void rw_vert_any_(std::integer_sequence<int, Rs...>, 
                                             double (&acc)[8]) {
   rdispatch<0, sizeof...(Rs) - 1>(r, [&](auto R) { rw_vert<decltype(R)::value, RW>(win, wp, acc); });
 }
-// BIN: binary dispatch (the register-window kernel, and the streamed kernels
-// with SIFT_BIN_STREAM); otherwise the compare chain.
-template <int RW, bool BIN = true, int... Rs>
+template <int RW, int... Rs>
 __device__ __forceinline__ void rw_horz_any_(std::integer_sequence<int, Rs...>, int r, const double* ra,
                                             const double* rb, const cdouble* wp, double (&out)[2][4]) {
-  if constexpr (BIN) {
-    rdispatch<0, sizeof...(Rs) - 1>(r, [&](auto R) { rw_horz<decltype(R)::value, RW>(ra, rb, wp, out); });
-  } else {
-    bool done = false;
-    ((!done && r == Rs ? (rw_horz<Rs, RW>(ra, rb, wp, out), done = true) : false), ...);
-  }
+  rdispatch<0, sizeof...(Rs) - 1>(r, [&](auto R) { rw_horz<decltype(R)::value, RW>(ra, rb, wp, out); });
 }
 // Streamed vertical pass of one strip column (k_gauss_rw<RW, true>): the
 // scale's own window rows y0 - r .. y0 + 7 + r loaded per scale from the base
@@ -1483,7 +1250,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_RW_WPE
   double* const L_next_seed = L.next_seed ? L.next_seed + im * L.seed_bs : nullptr;
   const double* const L_base = L.base + im * L.base_bs;
   const int bz = lb % L.G, bt = lb / L.G;
-  const int bx = bt % L.gx, by = bt / L.gx + L.by0;
+  const int bx = bt % L.gx, by = bt / L.gx;
   const int h = oc.h, w = oc.w;
   const int x0 = bx * G::TW, y0 = by * kRwRows;
   const int c = threadIdx.x;  // strip column
@@ -1517,7 +1284,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_RW_WPE
   const long long plane = (long long)h * w;
   const int s_begin = L.gb[bz], s_end = L.gb[bz + 1];
   const int s_first = max(0, s_begin - 1);
-  const bool st = !(L.dbg & 1);  // dbg 1: timing without plane stores
   double lprev[2][4];
   for (int s = s_first; s < s_end; ++s) {
     const cdouble* wp = (const cdouble*)(P.wts + oc.wofs[s]);
@@ -1542,8 +1308,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_RW_WPE
       int hc = hcg, h0 = hr0, h1 = hr1;
       asm volatile("" : "+v"(hc), "+v"(h0), "+v"(h1));  // per-scale opaque: no hoisted per-radius addresses
       double o[2][4];
-      rw_horz_any_<RW, !STREAM || SIFT_BIN_STREAM>(std::make_integer_sequence<int, RW + 1>{}, r, Vs + rw_row(h0) + 4 * hc,
-                                Vs + rw_row(h1) + 4 * hc, wp, o);
+      rw_horz_any_<RW>(std::make_integer_sequence<int, RW + 1>{}, r, Vs + rw_row(h0) + 4 * hc,
+                       Vs + rw_row(h1) + 4 * hc, wp, o);
       const int x = x0 + 4 * hc, nvalid = w - x;
       const unsigned pb = (unsigned)plane * 4u;
 #pragma unroll
@@ -1553,7 +1319,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_RW_WPE
         double d[4];
 #pragma unroll
         for (int q = 0; q < 4; ++q) d[q] = lprev[i][q] - o[i][q];
-        if (s >= s_begin && st) {
+        if (s >= s_begin) {
           if (L.vec) {
             const int voff = own ? (y * w + x) * 4 : 0x7ffffff0;  // dropped past the plane
             if (L_gauss)
@@ -1578,43 +1344,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(SIFT_RW_WPE
   }
 }
 
-// Octaves >= 1 through k_gauss_rw: radii up to SIFT_RW_R (the register
-// window of 8 + 2 RW rows per lane; default 12: octave 1 at 4K and 1080p,
-// 0.172 -> 0.158 ms at 4K; RW 24 for octave 2 measured slower, 0.097 ->
-// 0.100 ms: profiles/r4r_register_window_ab.txt), planes of at least 2
-// columns (SIFT_RW=0: k_gauss_dog, A/B builds).
-static int rw_width(const Pyramid& P, int o) {
-  const int R = P.oct[o].rmax;
-  return R <= 12 ? 12 : R <= 16 ? 16 : 24;
-}
-
-// Octaves >= 1 whose radii exceed the register window (SIFT_RW_R) up to 24
-// run k_gauss_rw with the streamed vertical pass (rw_vert_stream): 192-column
-// tiles in a 256-column strip instead of k_gauss_dog's 64-column tiles with
-// (64 + 2r) / 64 of the vertical work (SIFT_RWS=0: k_gauss_dog, A/B builds).
-// SIFT_RWS bit 0: radii 13..24; bit 1: also the register-window octaves
-// (radii <= 12) streamed.  Radii above 24 never run k_gauss_rw.
-static bool gauss_rws(const Pyramid& P, int o) {
-  static const int on = exp_knob("SIFT_RWS", SIFT_RWS_DEFAULT);
-  static const int rlim = exp_knob("SIFT_RW_R", 12);
-  const int r = P.oct[o].rmax;
-  if (!on || o < 1 || r > 24 || P.oct[o].w < 2 || gauss_keep_l64(P, o)) return false;
-  return r > std::min(rlim, 24) ? (on & 1) != 0 : (on & 2) != 0;
-}
-
-bool gauss_wide(const Pyramid& P, int o) {
-  static const int on = exp_knob("SIFT_RW", 1);
-  static const int rlim = exp_knob("SIFT_RW_R", 12);
-  return (on && o >= 1 && P.oct[o].w >= 2 && P.oct[o].rmax <= std::min(rlim, 24) && !gauss_keep_l64(P, o)) ||
-         gauss_rws(P, o);
-}
-
-static int rw_tile_w(const Pyramid& P, int o) {
-  const int RW = rw_width(P, o);
-  return RW <= 16 ? 224 : 192;
-}
-static size_t rw_lds(const Pyramid& P, int o) { (void)P; (void)o; return sizeof(double) * 2 * kRwStrip; }
-
 // Materialised octave-0 base (fp64), for octave-0 radii beyond kUR.
 __global__ __launch_bounds__(256) void k_upsample_base(const Pyramid P, double* __restrict__ b) {
   const int h = P.oct[0].h, w = P.oct[0].w;
@@ -1634,69 +1363,6 @@ __global__ __launch_bounds__(256) void k_dog_from_gauss(const float* __restrict_
   for (long long i = blockIdx.x * 256LL + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
     d[i] = (float)((double)g[i] - (double)g[i + plane]);
   }
-}
-
-bool gauss_needs_base0(const Pyramid& P) { return P.oct[0].rmax > kUR; }
-
-// Octaves o >= 1 whose largest radius reaches SIFT_L64_R (default 90; 0 =
-// never) also store their fp64 Gaussian planes: the exact passes read them
-// instead of recomputing 3x3x3 patches with 189- and 377-tap chains (8K O=6
-// S=5: octaves 4 and 5; at 4K octave 3, radius 47, it measured slower: 0.71 -> 0.74 ms pass).
-bool gauss_keep_l64(const Pyramid& P, int o) {
-  static const int rmin = exp_knob("SIFT_L64_R", 90);
-  return o >= 1 && rmin > 0 && P.oct[o].rmax >= rmin;
-}
-
-// Octaves o >= 1 whose largest radius reaches SIFT_VSPLIT_R (default 40; 0 =
-// never) run the split vertical pass (k_gauss_vert) before the tile kernel.
-bool gauss_vsplit(const Pyramid& P, int o) {
-  static const int rmin = exp_knob("SIFT_VSPLIT_R", 40);
-  return o >= 1 && rmin > 0 && P.oct[o].rmax >= rmin && !gauss_wide(P, o);
-}
-
-static bool staged0(const Pyramid& P, int o) { return o == 0 && !gauss_needs_base0(P); }
-
-// 96-column tiles (horz_full96) for octaves >= 1 whose radii all have
-// unrolled code and no split pass (SIFT_TW96=0: always 64, experiments).
-static int tile_w(const Pyramid& P, int o) {
-  static const int tw96 = exp_knob("SIFT_TW96", 1);
-  const Octave& oc = P.oct[o];
-  return (tw96 && o >= 1 && oc.rmax <= kUR96 && oc.w >= 2 && !gauss_vsplit(P, o)) ? 96 : kGX;
-}
-
-constexpr int kSW0 = 2 * (kCG - 1) + 8 + 6;   // octave-0 strip stride for rmax <= 8
-constexpr int kSW1 = 2 * (kCG - 1) + kUR + 6;  // ... rmax <= kUR
-
-// Strip row stride (doubles).  Octaves >= 1: covers the widest read of the
-// horizontal pass (generic path: 4 (kCG - 1) + round_up(2r + 4, 8)), and is
-// 2 mod 4 so that the two rows a ds_read_b128 phase reads fall in disjoint
-// bank halves.
-static int strip_stride(const Pyramid& P, int o) {
-  const int R = P.oct[o].rmax;
-  if (staged0(P, o)) return R <= 8 ? kSW0 : kSW1;
-  const int tw = tile_w(P, o);
-  int sw = R <= kUR1 ? tw + 2 * R + 4 : tw + 2 * R + 12;
-  if (sw % 4 == 0) sw += 2;
-  return sw;
-}
-
-static size_t staged_bytes(const Pyramid& P, int o) {
-  if (!staged0(P, o)) return 0;
-  const int R = P.oct[0].rmax;
-  return sizeof(double) * (size_t)(fl2(kGY - 1 + R) + cl2(R) + 1) * kBW0;
-}
-
-size_t gauss_lds_bytes(const Pyramid& P, int o, bool fused) {
-  if (!fused && gauss_wide(P, o)) return rw_lds(P, o);
-  return sizeof(double) * kGY * strip_stride(P, o) + staged_bytes(P, o) +
-         (fused ? sizeof(float) * 3 * kRingPlane : 0);
-}
-
-bool gauss_can_fuse(const Pyramid& P, int o) {
-  const Octave& oc = P.oct[o];
-  // staged0 implies octave 0, which never splits its scales (scale_groups)
-  return staged0(P, o) && oc.h >= 3 && oc.w >= 3 && P.S >= 1 &&
-         gauss_lds_bytes(P, o, true) <= 160 * 1024;
 }
 
 // Cost of one scale of a tile, in units of one fp64 tap per output of both
@@ -1735,43 +1401,162 @@ static int split_scales(const Pyramid& P, int o, int G, int* gb) {
   return best[G][NS];
 }
 
-// Scale groups per octave: small octaves split their scales so that enough
-// blocks fill the 256 CUs (octave 0 never splits: it is HBM-write bound and
-// every split recomputes a scale).  SIFT_GAUSS_GROUPS="g1,g2,..."
-// overrides the group count of octaves 1, 2, ... (experiments).
-static int scale_groups(const Pyramid& P, int o) {
-  static const std::vector<int> env = [] {
-    std::vector<int> v;
-#ifdef SIFT_EXPERIMENTS
-    if (const char* e = std::getenv("SIFT_GAUSS_GROUPS"))
-      for (const char* p = e; *p;) {
-        v.push_back(std::atoi(p));
-        while (*p && *p != ',') ++p;
-        if (*p) ++p;
-      }
-#endif
-    return v;
-  }();
-  if (o == 0) return 1;
-  if (o - 1 < (int)env.size() && env[o - 1] > 0) return std::min(env[o - 1], P.NS);
-  // Measured (4K, O=4, S=5; tools/experiments/gpu_groups.sh): every split adds the
-  // recomputed scale to the total work, so an octave splits only until it
-  // has ~1.5 blocks per CU -- 60x68 tiles: 1 group; 30x34: 1 (G=2: 116 us,
-  // G=4: 126-140 us, G=1: 103 us); 15x17: 2 (70.8 us; G=1 94 us, G=4 85 us).
-  const Octave& oc = P.oct[o];
-  const int tw = tile_w(P, o);
-  const long long tiles = (long long)((oc.w + tw - 1) / tw) * ((oc.h + kGY - 1) / kGY);
-  // (Split-pass octaves measured the same: 2048 instead of 400 blocks made
-  // 4K octave 3 0.054 -> 0.073 ms.)
-  int g = 1;
-  while (g < P.NS && tiles * g < 400) ++g;
-  return g;
+// ---------------------------------------------------------------------------
+// The launch plan of one octave (GaussPlan, sift_kernels.h): which kernel
+// runs it and with what geometry, decided here and nowhere else.
+// ---------------------------------------------------------------------------
+// Every instantiation the library launches, named once (all take (Pyramid,
+// GaussLaunch)); the k_gauss_dog ones first: they may need > 64 KiB of LDS.
+enum GaussKernel {
+  kKStaged8, kKStaged16, kKStaged8Fused, kKStaged16Fused, kKTiles, kKSplitTiles, kKNumDog,
+  kKWindow12 = kKNumDog, kKWindow16, kKWindow24, kKStreamed12, kKStreamed16, kKStreamed24
+};
+using GaussKernelFn = void (*)(const Pyramid, const GaussLaunch);
+static GaussKernelFn gauss_kernel(int k) {
+  switch (k) {
+    case kKStaged8: return k_gauss_dog<true, kSW0, 8, false>;
+    case kKStaged16: return k_gauss_dog<true, kSW1, kUR, false>;
+    case kKStaged8Fused: return k_gauss_dog<true, kSW0, 8, true>;
+    case kKStaged16Fused: return k_gauss_dog<true, kSW1, kUR, true>;
+    case kKTiles: return k_gauss_dog<false, 0, kUR1, false>;
+    case kKSplitTiles: return k_gauss_dog<false, 0, SIFT_VS_RMAX, false, true>;
+    case kKWindow12: return k_gauss_rw<12>;
+    case kKWindow16: return k_gauss_rw<16>;
+    case kKWindow24: return k_gauss_rw<24>;
+    case kKStreamed12: return k_gauss_rw<12, true>;
+    case kKStreamed16: return k_gauss_rw<16, true>;
+    default: return k_gauss_rw<24, true>;
+  }
 }
 
-template <bool O0, int SWC, int RMAX, bool XF>
-static void set_attr() {
-  (void)hipFuncSetAttribute((const void*)k_gauss_dog<O0, SWC, RMAX, XF>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            160 * 1024);
+// "a,b,..." from the environment of an experiments build (empty in the shipping library).
+static std::vector<int> exp_list(const char* name) {
+  std::vector<int> v;
+#ifdef SIFT_EXPERIMENTS
+  if (const char* e = std::getenv(name))
+    for (const char* p = e; *p;) {
+      v.push_back(std::atoi(p));
+      while (*p && *p != ',') ++p;
+      if (*p) ++p;
+    }
+#else
+  (void)name;
+#endif
+  return v;
+}
+
+GaussPlan gauss_plan(const Pyramid& P, int o) {
+  static const int rw_on = exp_knob("SIFT_RW", 1);
+  static const int rws_on = exp_knob("SIFT_RWS", SIFT_RWS_DEFAULT);
+  static const int rw_r = std::min(exp_knob("SIFT_RW_R", 12), 24);
+  static const int rw_minb = exp_knob("SIFT_RW_MINB", 600);
+  static const int l64_r = exp_knob("SIFT_L64_R", 90);
+  static const int vsplit_r = exp_knob("SIFT_VSPLIT_R", 40);
+  static const int xband = exp_knob("SIFT_XCD_BAND", -1);
+  static const int xband0 = exp_knob("SIFT_XCD_BAND0", 0);
+  static const std::vector<int> groups = exp_list("SIFT_GAUSS_GROUPS");  // "g1,g2,...": tile octaves 1, 2, ...
+  static const std::vector<int> bpc = exp_list("SIFT_GAUSS_BPC");        // "b1,b2,...": octaves 1, 2, ...
+  const Octave& oc = P.oct[o];
+  const int R = oc.rmax;
+  GaussPlan G{};
+  // Octaves o >= 1 whose largest radius reaches SIFT_L64_R (default 90; 0 =
+  // never) also store their fp64 Gaussian planes: the exact passes read them
+  // instead of recomputing 3x3x3 patches with 189- and 377-tap chains (8K O=6
+  // S=5: octaves 4 and 5; at 4K octave 3, radius 47, it measured slower: 0.71 -> 0.74 ms pass).
+  G.keep_l64 = o >= 1 && l64_r > 0 && R >= l64_r;
+  // Octaves >= 1 through k_gauss_rw (planes of at least 2 columns, no fp64
+  // planes).  Radii up to SIFT_RW_R keep the register window of 8 + 2 RW rows
+  // per lane (default 12: octave 1 at 4K and 1080p, 0.172 -> 0.158 ms at 4K;
+  // RW 24 for octave 2 measured slower, 0.097 -> 0.100 ms:
+  // profiles/r4r_register_window_ab.txt).  Radii above it up to 24 stream
+  // the window per scale (rw_vert_stream, profiles/r5k_streamed_rw_ab.txt):
+  // 192-column tiles in a 256-column strip instead of 64-column tiles with
+  // (64 + 2r) / 64 of the vertical work.  SIFT_RWS bit 0: radii above
+  // SIFT_RW_R; bit 1: the register-window octaves streamed too.  Radii above
+  // 24 never run k_gauss_rw.
+  const bool rw_ok = o >= 1 && oc.w >= 2 && !G.keep_l64;
+  const bool streamed = rw_ok && R <= 24 && (rws_on & (R > rw_r ? 1 : 2)) != 0;
+  const bool window = rw_ok && rw_on && R <= rw_r;
+  if (o == 0) {
+    // Radii above the unrolled range run on a materialised fp64 upsample of
+    // the input (4 H W doubles) instead of the staged input region.
+    G.path = R <= kUR ? kGaussStaged0 : kGaussBase0;
+  } else if (streamed || window) {
+    G.path = streamed ? kGaussStreamed : kGaussWindow;
+  } else {
+    // Largest radius from SIFT_VSPLIT_R (default 40; 0 = never): the split
+    // vertical pass (k_gauss_vert) before the tile kernel.
+    G.path = vsplit_r > 0 && R >= vsplit_r ? kGaussSplitTiles : kGaussTiles;
+  }
+  G.vsplit = G.path == kGaussSplitTiles;
+  if (G.path == kGaussWindow || G.path == kGaussStreamed) {
+    // (the streamed kernels use the tile geometry of their RW, as the window ones)
+    G.rw = R <= 12 ? 12 : R <= 16 ? 16 : 24;
+    G.tile_w = G.rw <= 16 ? RwGeom<16>::TW : RwGeom<24>::TW;
+    G.tile_rows = kRwRows;
+    G.sw = kRwSW;
+    G.lds = sizeof(double) * 2 * kRwStrip;
+    G.kernel = (streamed ? kKStreamed12 : kKWindow12) + (G.rw == 12 ? 0 : G.rw == 16 ? 1 : 2);
+  } else {
+    const bool staged = G.path == kGaussStaged0;
+    G.tile_w = kGX;
+    G.tile_rows = kGY;
+    // Strip row stride (doubles).  Octaves >= 1: covers the widest read of
+    // the horizontal pass (generic path: 4 (kCG - 1) + round_up(2r + 4, 8)),
+    // and is 2 mod 4 so that the two rows a ds_read_b128 phase reads fall in
+    // disjoint bank halves.
+    if (staged) {
+      G.sw = R <= 8 ? kSW0 : kSW1;
+    } else {
+      G.sw = R <= kUR1 ? kGX + 2 * R + 4 : kGX + 2 * R + 12;
+      if (G.sw % 4 == 0) G.sw += 2;
+    }
+    G.lds = sizeof(double) * kGY * G.sw +
+            (staged ? sizeof(double) * (size_t)(fl2(kGY - 1 + R) + cl2(R) + 1) * kBW0 : 0);  // + the staged region
+    G.zero = R > (staged ? kUR : kUR1);  // generic-radius path present
+    G.kernel = staged ? (R <= 8 ? kKStaged8 : kKStaged16) : G.vsplit ? kKSplitTiles : kKTiles;
+    // Fused extrema decisions: the staged octave 0 (one scale group), a plane
+    // of at least 3 x 3, the fp32 DoG ring after the strip and the region.
+    G.lds_fused = G.lds + sizeof(float) * 3 * kRingPlane;
+    G.can_fuse = staged && oc.h >= 3 && oc.w >= 3 && P.S >= 1 && G.lds_fused <= kGaussMaxLds;
+  }
+  G.gx = (oc.w + G.tile_w - 1) / G.tile_w;
+  G.gy = (oc.h + G.tile_rows - 1) / G.tile_rows;
+  // Scale groups: small octaves split their scales so that enough blocks fill
+  // the 256 CUs; every group recomputes the scale before it.  Octave 0 never
+  // splits (it is HBM-write bound).
+  const long long tiles = (long long)G.gx * G.gy;
+  G.G = 1;
+  if (G.rw) {
+    while (G.G < P.NS && tiles * G.G < rw_minb) ++G.G;  // fewer than SIFT_RW_MINB tiles x groups
+  } else if (o >= 1 && o - 1 < (int)groups.size() && groups[o - 1] > 0) {
+    G.G = std::min(groups[o - 1], P.NS);
+  } else if (o >= 1) {
+    // Measured (4K, O=4, S=5; tools/experiments/gpu_groups.sh): every split adds the
+    // recomputed scale to the total work, so an octave splits only until it
+    // has ~1.5 blocks per CU -- 60x68 tiles: 1 group; 30x34: 1 (G=2: 116 us,
+    // G=4: 126-140 us, G=1: 103 us); 15x17: 2 (70.8 us; G=1 94 us, G=4 85 us).
+    // (Split-pass octaves measured the same: 2048 instead of 400 blocks made
+    // 4K octave 3 0.054 -> 0.073 ms.)
+    while (G.G < P.NS && tiles * G.G < 400) ++G.G;
+  }
+  split_scales(P, o, G.G, G.gb);
+  // XCD-banded tile order for octaves >= 1 (SIFT_XCD_BAND: bit o-1 of the
+  // value; default all).  Measured (4K, O=4, S=5): isolated pass 0.748 ->
+  // 0.730 ms, pipelined bench +0.5-1 % (tools/gpu_envab.sh).
+  G.xcd_band = o >= 1 ? (xband >> (o - 1)) & 1 : xband0;
+  // Blocks per CU of the octave-o >= 1 launches: the vertical passes re-read
+  // the base window of every active block once per scale, and the active
+  // blocks of an XCD share its 4 MiB L2.  SIFT_GAUSS_BPC caps the blocks per
+  // CU by padding the dynamic LDS (experiments; 0 = no cap).
+  if (o >= 1 && o - 1 < (int)bpc.size() && bpc[o - 1] > 0)
+    G.lds = std::max(G.lds, kGaussMaxLds / bpc[o - 1] - 1024);
+  static const char* const names[] = {
+      "k_gauss_dog<octave0>", "k_gauss_dog<octave0>", kGaussFusedName, kGaussFusedName, "k_gauss_dog<64>",
+      "k_gauss_vert + k_gauss_dog<64>", "k_gauss_rw<12>", "k_gauss_rw<16>", "k_gauss_rw<24>",
+      "k_gauss_rw<12,true>", "k_gauss_rw<16,true>", "k_gauss_rw<24,true>"};
+  G.kname = G.path == kGaussBase0 ? "k_upsample_base + k_gauss_dog<octave0,fp64 base>" : names[G.kernel];
+  return G;
 }
 
 // The base of octave o+1 alone (sift_detect_from_seed_range_device: an
@@ -1855,155 +1640,38 @@ hipError_t launch_upsample_base(const Pyramid& P, double* base0, hipStream_t st)
   return hipGetLastError();
 }
 
-int gauss_tile_rows(const Pyramid& P, int o) { return (P.oct[o].h + kGY - 1) / kGY; }
-
-// Blocks per CU of the octave-o >= 1 launches: the vertical passes re-read
-// the base window of every active block once per scale, and the active
-// blocks of an XCD share its 4 MiB L2.  SIFT_GAUSS_BPC="b1,b2,..." caps the
-// blocks per CU of octaves 1, 2, ... by padding the dynamic LDS
-// (experiments; 0 = no cap).
-static size_t occupancy_lds(int o, size_t lds) {
-  static const std::vector<int> bpc = [] {
-    std::vector<int> v;
-#ifdef SIFT_EXPERIMENTS
-    if (const char* e = std::getenv("SIFT_GAUSS_BPC"))
-      for (const char* p = e; *p;) {
-        v.push_back(std::atoi(p));
-        while (*p && *p != ',') ++p;
-        if (*p) ++p;
-      }
-#endif
-    return v;
-  }();
-  if (o < 1 || o - 1 >= (int)bpc.size() || bpc[o - 1] <= 0) return lds;
-  const size_t cap = (size_t)160 * 1024 / bpc[o - 1] - 1024;
-  return std::max(lds, cap);
-}
-
-hipError_t launch_gauss_dog(const Pyramid& P, GaussLaunch L, hipStream_t st, int ty_begin, int ty_end,
-                            const char** kname) {
-  const char* kn_dummy = nullptr;
-  const char*& kn = kname ? *kname : kn_dummy;
-  static_assert(kGY == kGaussTileRows, "tile rows");
+// Fills the launch fields of L from the plan and launches; decides nothing.
+hipError_t launch_gauss_dog(const Pyramid& P, const GaussPlan& G, GaussLaunch L, hipStream_t st) {
   const Octave& oc = P.oct[L.o];
   if (L.nimg < 1) L.nimg = 1;
-  if (L.fuse && !gauss_can_fuse(P, L.o)) return hipErrorInvalidValue;
-  if (L.nimg > 1 && (L.fuse || ty_end >= 0)) return hipErrorInvalidValue;  // batches: whole octaves, no fused decisions
-  if (!L.fuse && !L.vsplit && gauss_wide(P, L.o)) {
-    if (!L.base) return hipErrorInvalidValue;
-    const int RW = rw_width(P, L.o), tw = rw_tile_w(P, L.o);
-    L.gx = (oc.w + tw - 1) / tw;
-    L.gy = (oc.h + kRwRows - 1) / kRwRows;
-    // Scale groups while the octave has fewer than SIFT_RW_MINB tiles x
-    // groups (each group recomputes the scale before it).
-    static const int minb = exp_knob("SIFT_RW_MINB", 600);
-    int G = 1;
-    while (G < P.NS && (long long)L.gx * L.gy * G < minb) ++G;
-    split_scales(P, L.o, G, L.gb);
-    L.G = G;
-    L.by0 = 0;
-    if (ty_end >= 0) {  // a band of kGY-row tile rows: the same rows in 8-row tiles
-      if (ty_begin < 0 || ty_begin >= ty_end) return hipErrorInvalidValue;
-      const int rb = ty_begin * (kGY / kRwRows), re = std::min(L.gy, ty_end * (kGY / kRwRows));
-      if (rb >= re) return hipErrorInvalidValue;
-      L.by0 = rb;
-      L.gy = re - rb;
-    }
-    static const int xband = exp_knob("SIFT_XCD_BAND", -1);
-    L.xcd_band = (xband >> (L.o - 1)) & 1;
-    L.sw = kRwSW;
-    static const int dbg = exp_knob("SIFT_GAUSS_DBG", 0);
-    L.dbg = dbg;
-    const bool a16 = !((reinterpret_cast<uintptr_t>(L.dog)) & 15) &&
-                     (!L.gauss || !((reinterpret_cast<uintptr_t>(L.gauss)) & 15)) &&
-                     (L.nimg <= 1 || ((L.dog_bs & 3) == 0 && (!L.gauss || (L.gauss_bs & 3) == 0)));  // every image's planes
-    L.vec = (a16 && (oc.w & 3) == 0 && 4.0 * oc.h * oc.w < 2147483648.0) ? 1 : 0;
-    L.zero = 0;
-    const dim3 grid(L.gx * L.gy * L.G * L.nimg);
-    const size_t lds = occupancy_lds(L.o, rw_lds(P, L.o));
-    // (the streamed kernels use the tile geometry of their RW, as the window ones)
-    if (gauss_rws(P, L.o)) {
-      if (RW == 12) hipLaunchKernelGGL((k_gauss_rw<12, true>), grid, dim3(256), lds, st, P, L);
-      else if (RW == 16) hipLaunchKernelGGL((k_gauss_rw<16, true>), grid, dim3(256), lds, st, P, L);
-      else hipLaunchKernelGGL((k_gauss_rw<24, true>), grid, dim3(256), lds, st, P, L);
-      kn = RW == 12 ? "k_gauss_rw<12,true>" : RW == 16 ? "k_gauss_rw<16,true>" : "k_gauss_rw<24,true>";
-    } else {
-      if (RW == 12) hipLaunchKernelGGL(k_gauss_rw<12>, grid, dim3(256), lds, st, P, L);
-      else if (RW == 16) hipLaunchKernelGGL(k_gauss_rw<16>, grid, dim3(256), lds, st, P, L);
-      else hipLaunchKernelGGL(k_gauss_rw<24>, grid, dim3(256), lds, st, P, L);
-      kn = RW == 12 ? "k_gauss_rw<12>" : RW == 16 ? "k_gauss_rw<16>" : "k_gauss_rw<24>";
-    }
-    return hipGetLastError();
-  }
-  const int G = scale_groups(P, L.o);
-  split_scales(P, L.o, G, L.gb);
-  const int tw = tile_w(P, L.o);
-  L.gx = L.fuse ? fused_words_per_row(oc.w) : (oc.w + tw - 1) / tw;
-  L.gy = L.fuse ? (oc.h - 2 + kFY - 1) / kFY : (oc.h + kGY - 1) / kGY;
-  L.by0 = 0;
-  if (ty_end >= 0) {  // a band of tile rows
-    if (L.fuse || L.vsplit || ty_begin < 0 || ty_end > L.gy || ty_begin >= ty_end) return hipErrorInvalidValue;
-    L.by0 = ty_begin;
-    L.gy = ty_end - ty_begin;
-  }
-  L.G = L.fuse ? 1 : G;
+  if (L.fuse && (!G.can_fuse || L.nimg > 1)) return hipErrorInvalidValue;  // batches: no fused decisions
+  if (G.path != kGaussStaged0 && !L.base) return hipErrorInvalidValue;
+  if (G.vsplit != (L.vsplit != nullptr)) return hipErrorInvalidValue;
+  L.gx = L.fuse ? fused_words_per_row(oc.w) : G.gx;
+  L.gy = L.fuse ? (oc.h - 2 + kFY - 1) / kFY : G.gy;
   if (L.fuse && L.gx != L.X.nw) return hipErrorInvalidValue;
-  // XCD-banded tile order for octaves >= 1 (SIFT_XCD_BAND: bit o-1 of the
-  // value; default all).  Measured (4K, O=4, S=5): isolated pass 0.748 ->
-  // 0.730 ms, pipelined bench +0.5-1 % (tools/gpu_envab.sh).
-  static const int xband = exp_knob("SIFT_XCD_BAND", -1);
-  static const int xband0 = exp_knob("SIFT_XCD_BAND0", 0);
-  L.xcd_band = L.o >= 1 ? ((xband >> (L.o - 1)) & 1) : xband0;
-  const dim3 grid(L.gx * L.gy * L.G * L.nimg);
-  const size_t lds = gauss_lds_bytes(P, L.o, L.fuse != 0);
-  static bool attr_set = false;
-  if (!attr_set) {  // allow > 64 KiB of dynamic LDS (gfx950 has 160 KiB per CU)
-    set_attr<true, kSW0, 8, false>();
-    set_attr<true, kSW1, kUR, false>();
-    set_attr<false, 0, kUR1, false>();
-    (void)hipFuncSetAttribute((const void*)k_gauss_dog<false, 0, SIFT_VS_RMAX, false, kGX, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)k_gauss_dog<false, 0, kUR96, false, 96>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    set_attr<true, kSW0, 8, true>();
-    set_attr<true, kSW1, kUR, true>();
-    attr_set = true;
-  }
-  L.sw = strip_stride(P, L.o);
-  static const int dbg = exp_knob("SIFT_GAUSS_DBG", 0);
-  L.dbg = dbg;
+  L.G = G.G;
+  std::copy(G.gb, G.gb + G.G + 1, L.gb);
+  L.xcd_band = G.xcd_band;
+  L.sw = G.sw;
+  L.zero = G.zero;
   const bool a16 = !((reinterpret_cast<uintptr_t>(L.dog)) & 15) &&
                    (!L.gauss || !((reinterpret_cast<uintptr_t>(L.gauss)) & 15)) &&
                    (L.nimg <= 1 || ((L.dog_bs & 3) == 0 && (!L.gauss || (L.gauss_bs & 3) == 0)));  // every image's planes
   L.vec = (a16 && (oc.w & 3) == 0 && 4.0 * oc.h * oc.w < 2147483648.0) ? 1 : 0;
-  L.zero = oc.rmax > (staged0(P, L.o) ? kUR : kUR1) ? 1 : 0;
-  if (L.vsplit) {
-    if (L.o == 0 || !L.base) return hipErrorInvalidValue;
+  static bool attr_set = false;
+  if (!attr_set) {  // allow > 64 KiB of dynamic LDS (gfx950 has 160 KiB per CU)
+    for (int k = 0; k < kKNumDog; ++k)
+      (void)hipFuncSetAttribute((const void*)gauss_kernel(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kGaussMaxLds);
+    attr_set = true;
+  }
+  if (G.vsplit)
     hipLaunchKernelGGL(k_gauss_vert, dim3((oc.w + kGX - 1) / kGX, (oc.h + kVertRows - 1) / kVertRows, P.NS * L.nimg),
                        dim3(256), 0, st, P, L.o, L.base, L.vsplit, L.base_bs, L.vsplit_bs);
-  }
-  if (L.fuse) {  // staged octave 0 (gauss_can_fuse)
-    if (L.sw == kSW0) hipLaunchKernelGGL((k_gauss_dog<true, kSW0, 8, true>), grid, dim3(256), lds, st, P, L);
-    else hipLaunchKernelGGL((k_gauss_dog<true, kSW1, kUR, true>), grid, dim3(256), lds, st, P, L);
-    kn = "k_gauss_dog<octave0,fused extrema>";
-  } else if (tw == 96) {
-    hipLaunchKernelGGL((k_gauss_dog<false, 0, kUR96, false, 96>), grid, dim3(256), occupancy_lds(L.o, lds), st, P, L);
-    kn = "k_gauss_dog<96>";
-  } else if (staged0(P, L.o) && L.sw == kSW0) {
-    hipLaunchKernelGGL((k_gauss_dog<true, kSW0, 8, false>), grid, dim3(256), lds, st, P, L);
-    kn = "k_gauss_dog<octave0>";
-  } else if (staged0(P, L.o)) {
-    hipLaunchKernelGGL((k_gauss_dog<true, kSW1, kUR, false>), grid, dim3(256), lds, st, P, L);
-    kn = "k_gauss_dog<octave0>";
-  } else {
-    if (L.vsplit) {
-      hipLaunchKernelGGL((k_gauss_dog<false, 0, SIFT_VS_RMAX, false, kGX, true>), grid, dim3(256),
-                         occupancy_lds(L.o, lds), st, P, L);
-    } else {
-      hipLaunchKernelGGL((k_gauss_dog<false, 0, kUR1, false>), grid, dim3(256), occupancy_lds(L.o, lds), st, P, L);
-    }
-    kn = L.vsplit ? "k_gauss_vert + k_gauss_dog<64>" : L.o == 0 ? "k_gauss_dog<octave0,fp64 base>" : "k_gauss_dog<64>";
-  }
+  const int k = L.fuse ? G.kernel + (kKStaged8Fused - kKStaged8) : G.kernel;
+  hipLaunchKernelGGL(gauss_kernel(k), dim3(L.gx * L.gy * L.G * L.nimg), dim3(256), L.fuse ? G.lds_fused : G.lds, st, P,
+                     L);
   return hipGetLastError();
 }
 

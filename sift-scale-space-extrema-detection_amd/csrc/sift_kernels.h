@@ -41,16 +41,14 @@ struct GaussLaunch {
   int next_w;
   const double* base; // fp64 octave base h x w (o >= 1: the seed; o == 0: only when materialised)
   double* l64;        // plane (o, 0) of the kept fp64 Gaussian planes, nullptr = not kept
-  double* vsplit;     // large radii (gauss_vsplit): fp64 scratch of NS vertical-sum planes h x w, filled by a
+  double* vsplit;     // split pass (GaussPlan.vsplit): fp64 scratch of NS vertical-sum planes h x w, filled by a
                       // separate launch; the tile kernel copies its strip from it (nullptr = one pass)
-  // filled by launch_gauss_dog
+  // filled by launch_gauss_dog from the GaussPlan
   int sw;             // strip row stride (doubles)
   int vec;            // float4 plane stores are aligned
   int zero;           // strips need zeroing (generic-radius path present)
-  int dbg;            // timing experiments (SIFT_GAUSS_DBG): bit 0 = no plane stores
   int gb[kMaxScales + 1];  // scale groups: group g computes scales gb[g] .. gb[g+1]-1
   int gx, gy, G;      // tiles per row, tile rows, scale groups (1D grid of gx gy G blocks)
-  int by0;            // first tile row of this launch (a band of tile rows by0 .. by0 + gy - 1)
   int xcd_band;       // 1: block -> tile so that each XCD runs a contiguous band of tile rows
   // batch: nimg images in one launch (blocks image-major); image im's
   // pointers are the fields above + im * these element strides
@@ -194,40 +192,48 @@ struct BandOrder {
 hipError_t launch_band_items(const Pyramid& P, const BandOrder& B, hipStream_t st);
 hipError_t launch_band_fill(const Pyramid& P, const BandOrder& B, hipStream_t st);
 
-size_t gauss_lds_bytes(const Pyramid& P, int o, bool fused = false);
-// Octave o can run with its extrema decisions fused (GaussLaunch.fuse):
-// octave 0 on the staged path, one scale group, a plane of at least 3 x 3.
-bool gauss_can_fuse(const Pyramid& P, int o);
-// Octave 0 radii above the unrolled range run on a materialised fp64 upsample
-// of the input (4 H W doubles) instead of the staged input region.
-bool gauss_needs_base0(const Pyramid& P);
+// Everything that is decided about octave o's Gaussian+DoG pass, built once
+// per geometry by gauss_plan (the context holds one per octave) and read by
+// the launcher and by the stages that size buffers for it.
+enum GaussPath {
+  kGaussStaged0,     // octave 0 from the staged input region (k_gauss_dog<octave0>; strip stride kSW0 / kSW1)
+  kGaussBase0,       // octave 0 on a materialised fp64 upsample (launch_upsample_base first), 64-column tiles
+  kGaussTiles,       // 64-column tiles (k_gauss_dog<64>)
+  kGaussSplitTiles,  // split vertical pass (k_gauss_vert) + 64-column tiles
+  kGaussWindow,      // register-window tiles (k_gauss_rw<RW>)
+  kGaussStreamed,    // ... with the window streamed per scale (k_gauss_rw<RW,true>)
+};
+constexpr size_t kGaussMaxLds = 160 * 1024;  // LDS of one gfx950 CU: a plan with more cannot launch
+constexpr const char* kGaussFusedName = "k_gauss_dog<octave0,fused extrema>";
+struct GaussPlan {
+  GaussPath path;
+  int kernel;              // the instantiation (sift_gauss.hip)
+  const char* kname;       // its launches, e.g. "k_gauss_rw<12>" or "k_gauss_vert + k_gauss_dog<64>" (static string;
+                           // sift_last_pass_kernels); a fused launch is kGaussFusedName
+  int rw;                  // k_gauss_rw: window radius RW (12, 16, 24); 0 otherwise
+  int tile_w, tile_rows;   // output columns x rows per block
+  int gx, gy;              // tiles per row, tile rows (unfused)
+  int sw;                  // strip row stride (doubles)
+  size_t lds, lds_fused;   // dynamic LDS bytes of the launch, unfused / fused
+  int zero;                // strips need zeroing (generic-radius path present)
+  bool keep_l64;           // the octave stores its fp64 Gaussian planes too (GaussLaunch.l64): the exact passes
+                           // then read the patch values instead of recomputing them
+  bool vsplit;             // needs the split pass's scratch (GaussLaunch.vsplit: NS x h x w doubles)
+  bool can_fuse;           // may run with its extrema decisions fused (GaussLaunch.fuse)
+  int xcd_band;            // GaussLaunch.xcd_band
+  int G;                   // scale groups; group g computes scales gb[g] .. gb[g+1]-1
+  int gb[kMaxScales + 1];
+};
+GaussPlan gauss_plan(const Pyramid& P, int o);
+hipError_t launch_gauss_dog(const Pyramid& P, const GaussPlan& G, GaussLaunch L, hipStream_t st);
 hipError_t launch_upsample_base(const Pyramid& P, double* base0, hipStream_t st);
 // The base of octave o+1 from octave o's base alone (no planes): L_o[S] at
 // even rows / columns; vrow: seed_only_scratch(P, o) doubles.
 size_t seed_only_scratch(const Pyramid& P, int o);
 hipError_t launch_seed_only(const Pyramid& P, int o, const double* base, double* vrow, double* next, hipStream_t st);
-// ty_end >= 0: only tile rows [ty_begin, ty_end) of the octave (a band;
-// not for fused or split-pass octaves).
-// kname (optional): the launches this call made, e.g. "k_gauss_rw<12>" or
-// "k_gauss_vert + k_gauss_dog<64>" (a static string; sift_last_pass_kernels).
-hipError_t launch_gauss_dog(const Pyramid& P, GaussLaunch L, hipStream_t st, int ty_begin = 0, int ty_end = -1,
-                            const char** kname = nullptr);
-int gauss_tile_rows(const Pyramid& P, int o);  // tile rows of octave o's Gaussian launch
-constexpr int kGaussTileRows = 32;             // output rows per tile row
 // Tile columns of a fused launch over a w-column octave (= bitmap words per row).
 inline int fused_words_per_row(int w) { return w > 2 ? (w - 2 + kFX - 1) / kFX : 1; }
 hipError_t launch_dog_from_gauss(const float* g, float* d, long long plane, int nd, hipStream_t st);
-
-// Octave o stores its fp64 Gaussian planes too (GaussLaunch.l64): the exact
-// passes then read the patch values instead of recomputing them.
-bool gauss_keep_l64(const Pyramid& P, int o);
-
-// Octave o runs the split vertical pass (GaussLaunch.vsplit scratch: NS x h x
-// w doubles).
-bool gauss_vsplit(const Pyramid& P, int o);
-// Octave o (>= 1) runs k_gauss_rw (register-window tiles, 224 columns x 8 rows; no split pass).
-bool gauss_wide(const Pyramid& P, int o);
-// The octave-1 base straight from the input (bit-identical to the octave-0 launch's seeds).
 
 // Fills the unit table of L and launches the scan; returns the launch error.
 // The octaves [o_begin, o_end) of L.G must have the scan's word geometry

@@ -189,6 +189,49 @@ def test_pass_kernels_record(gpu_ctx, W, H):
             np.testing.assert_array_equal(gpu_ctx.plane(sift_amd.PLANE_DOG, 3, s), r.dog[3][s].astype(np.float32))
 
 
+_SPLIT = "k_gauss_vert + k_gauss_dog<64>"
+_PASS_PATHS = [
+    # (O, S, min_blur), largest radius per octave, launches per octave
+    ((4, 5, 0.8), [6, 12, 23, 47],
+     ["k_gauss_dog<octave0>", "k_gauss_rw<12>", "k_gauss_rw<24,true>", _SPLIT]),
+    ((5, 3, 0.8), [7, 14, 29, 58, 116],
+     ["k_gauss_dog<octave0>", "k_gauss_rw<16,true>", "k_gauss_dog<64>", _SPLIT, _SPLIT]),
+    ((4, 2, 0.8), [9, 19, 37, 74],
+     ["k_gauss_dog<octave0>", "k_gauss_rw<24,true>", "k_gauss_dog<64>", _SPLIT]),
+    ((3, 3, 2.5), [24, 45, 90],
+     ["k_upsample_base + k_gauss_dog<octave0,fp64 base>", _SPLIT, _SPLIT]),
+]
+
+
+@pytest.mark.timeout(120)
+@pytest.mark.parametrize("params,rmax,kernels", _PASS_PATHS, ids=["O4S5", "O5S3", "O4S2", "O3S3mb2.5"])
+def test_pass_kernels_every_path(gpu_ctx, params, rmax, kernels):
+    """One 160x120 image per launch path of the Gaussian pass: octave 0 staged
+    with either strip stride (largest radius <= 8, 9..16) or on the
+    materialised fp64 base (> 16); octaves >= 1 through the register window
+    (<= 12), the streamed window (13..24, RW 16 and 24), the 64-column tiles
+    (25..39) and the split vertical pass + tiles (>= 40; >= 90 also keeps the
+    fp64 planes).  The radii are asserted so that a schedule change cannot
+    move a case onto another path; every Gaussian and DoG plane equals the
+    oracle's in the HIP path's operation order, bit for bit."""
+    from sift_amd.shard import octave_radii
+    p = sift_amd.make_params(*params)
+    assert [max(r) for r in octave_radii(p)] == rmax
+    img = blob_image(160, 120, seed=3)
+    gpu_ctx.build_scale_space(img, p)
+    parts = dict(e.split(": ", 1) for e in gpu_ctx.pass_kernels().split("; "))
+    assert parts == {"o%d" % o: k for o, k in enumerate(kernels)}, parts
+    r = orc.OracleRun(img, oracle_params(p), orc.CONV_SEPARABLE_FMA_VH, threads=host_threads())
+    S = p.scales_per_octave
+    for o in range(p.num_octaves):
+        for s in range(S + 3):
+            np.testing.assert_array_equal(gpu_ctx.plane(sift_amd.PLANE_GAUSS, o, s), r.gauss[o][s].astype(np.float32),
+                                          err_msg="gauss o%d s%d" % (o, s))
+        for s in range(S + 2):
+            np.testing.assert_array_equal(gpu_ctx.plane(sift_amd.PLANE_DOG, o, s), r.dog[o][s].astype(np.float32),
+                                          err_msg="dog o%d s%d" % (o, s))
+
+
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("W,H,O,S,seed", [(3840, 2160, 4, 5, 42), (333, 517, 4, 3, 4), (64, 48, 3, 3, 5)])
 def test_fused_extrema_flag_same_results(gpu_ctx, W, H, O, S, seed):
