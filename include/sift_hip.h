@@ -435,6 +435,63 @@ int sift_plane_image_device(struct sift_ctx *ctx, int kind, int octave, int scal
 int sift_copy_keypoint_origins_device(struct sift_ctx *ctx, int32_t *d_dst, size_t cap, size_t *n_out);
 int sift_copy_next_seed_device(struct sift_ctx *ctx, double *d_dst, size_t cap, int row_begin, int row_end);
 
+/* ---- Orientation assignment and descriptors -------------------------------
+ *
+ * The reference stops at refinement (readme.md:11); these two stages follow
+ * Rey-Otero & Delbracio, "Anatomy of the SIFT Method" (IPOL 2014), algorithms
+ * 11 and 12, in fp64 on the context's fp32 Gaussian planes, in octave-local
+ * pixel units (x = abs_x / 2^(octave-1), likewise y and sigma; plane =
+ * SIFT_PLANE_GAUSS (octave, scale_level)).  Results are bit-identical from
+ * run to run.  SIFT_ABI_VERSION stays 9: a caller detects these entry points
+ * by symbol (dlsym / hasattr), not by version.  The constants are fixed;
+ * there is no setter. */
+#define SIFT_ORI_LAMBDA 1.5      /* Gaussian window sigma = lambda * sigma; box radius 3 * that */
+#define SIFT_ORI_BINS 36
+#define SIFT_ORI_SMOOTH 6        /* circular (1,1,1)/3 passes over the histogram */
+#define SIFT_ORI_PEAK_RATIO 0.8
+#define SIFT_ORI_MAX_PEAKS 18    /* strict circular maxima of 36 bins */
+#define SIFT_DESC_LAMBDA 6.0     /* Gaussian window sigma = lambda * sigma; cells are 3 sigma wide */
+#define SIFT_DESC_CELLS 4        /* 4 x 4 cells */
+#define SIFT_DESC_ORI 8          /* orientation bins per cell */
+#define SIFT_DESC_CAP 0.2        /* clamp at cap * norm, then renormalise */
+#define SIFT_DESC_BYTES 128      /* byte (i*4 + j)*8 + k: cell row i, cell column j, bin k */
+
+/* One reference orientation of keypoint `keypoint` (its index in the list
+ * sift_copy_keypoints returns): the histogram peak in bin `bin`, interpolated
+ * to theta in [0, 2 pi).  Records are in keypoint order, then ascending bin;
+ * a keypoint whose 3 * lambda * sigma box leaves [1, w-2] x [1, h-2] has none. */
+typedef struct {
+  int32_t keypoint;
+  int32_t bin;
+  double theta;
+} sift_orientation; /* 16 bytes */
+
+/* Orientations of the keypoints of the last refinement / detection.  Records
+ * stay on the device when out == NULL (*n_out still returned).
+ * SIFT_E_CAPACITY: *n_out = required count, nothing written.  SIFT_E_STATE:
+ * no refinement yet, or the Gaussian planes were not materialised
+ * (SIFT_F_SKIP_GAUSS_PLANES, sift_load_dog).  SIFT_E_UNSUPPORTED: a batch, a
+ * row origin or owned rows set, or a seed-range detection whose leading
+ * octaves have no planes. */
+int sift_orient(struct sift_ctx *ctx, sift_orientation *out, size_t cap, size_t *n_out);
+
+/* One 128-byte descriptor per record of the last sift_orient (SIFT_E_STATE
+ * without one).  A record whose descriptor box leaves [1, w-2] x [1, h-2] is
+ * not described: 128 zero bytes, described[r] = 0 (else 1).  desc == NULL
+ * keeps the results on the device; `described` may be NULL; cap is in
+ * records.  *n_out = records, *n_described = described records. */
+int sift_describe(struct sift_ctx *ctx, uint8_t *desc, uint8_t *described, size_t cap, size_t *n_out,
+                  size_t *n_described);
+
+/* Device pointers of the last sift_orient + sift_describe results (n records;
+ * valid until the next orient / describe / build / detect). */
+int sift_device_features(struct sift_ctx *ctx, const sift_orientation **d_ori, const uint8_t **d_desc,
+                         const uint8_t **d_described, size_t *n);
+
+/* Device time of the last sift_orient (histograms, scan, emission) and
+ * sift_describe, milliseconds. */
+int sift_last_feature_timings(struct sift_ctx *ctx, double *orient_ms, double *describe_ms);
+
 /* Wait for all work queued on ctx's stream. */
 int sift_synchronize(struct sift_ctx *ctx);
 

@@ -217,6 +217,15 @@ struct sift_ctx {
   DBuf kp_soa;                                 // keypoint field arrays for a DMA into registered host arrays
   DBuf xseed, kp_key;                          // next-octave base, keypoint origins
   DBuf merge_tab;                              // sift_merge_keypoint_blocks_device tables
+  // orientation / descriptor stages (sift_feature.hip)
+  bool have_kp = false;                        // a refinement has settled on this pyramid: kp / n_kp are its list
+  bool have_ori = false, have_desc = false;    // ori / desc hold the records of that list
+  size_t n_ori = 0, n_desc_ok = 0;             // records, described records
+  DBuf ori_count, ori_off, ori_mask, ori_theta;  // per keypoint: peaks, their exclusive scan, bins, angles
+  DBuf ori, desc, desc_ok, desc_n;             // records, 128 bytes each, described flags, described count
+  HBuf hfeat;                                  // pinned: the two counts
+  hipEvent_t ev_f[4]{};                        // around the orientation stage [0, 1] and the descriptor stage [2, 3]
+  double orient_ms = 0, describe_ms = 0;
   DBuf counters, temp;
   DBuf rgba, alpha, display, mm_parts;         // image products (sift_image.hip)
   unsigned* h_counters = nullptr;              // pinned mirror of counters (+ per-block keypoint counts at kBlk)
@@ -238,6 +247,8 @@ struct sift_ctx {
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_go)
+      if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_f)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_pl)
       if (e) (void)hipEventDestroy(e);
@@ -791,6 +802,7 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
   ctx->dog_source = kNative;
   ctx->have_gauss = keep_gauss;
   ctx->have_cand = false;
+  ctx->have_kp = ctx->have_ori = ctx->have_desc = false;
   ctx->has_xseed = xseed;
   return SIFT_OK;
 }
@@ -896,6 +908,7 @@ static int finish_load(sift_ctx* ctx, bool have_gauss) {
   ctx->planes_first = 0;
   ctx->have_gauss = have_gauss;
   ctx->have_cand = false;
+  ctx->have_kp = ctx->have_ori = ctx->have_desc = false;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SIFT_OK;
 }
@@ -1231,6 +1244,7 @@ static int refine_enqueue(sift_ctx* ctx) {
   ctx->counters_zeroed = false;
   ctx->n_kp = 0;
   ctx->n_sing = 0;
+  ctx->have_kp = ctx->have_ori = ctx->have_desc = false;
   if (cap > 0) {
     RefineLaunch R{};
     R.cand_key = ctx->cand_key.as<unsigned>();
@@ -1315,6 +1329,8 @@ static int refine_settle(sift_ctx* ctx) {
   ctx->n_exact += h[kCntUnc];
   ctx->n_kp = cap > 0 ? h[kCntKp] : 0;
   ctx->n_sing = h[kCntSing];
+  ctx->have_kp = true;
+  ctx->have_ori = ctx->have_desc = false;
   ctx->blk_counts.assign((size_t)std::max(1, ctx->P.nimg) * ctx->P.O * ctx->P.S, 0);
   if (cap > 0)
     for (size_t b = 0; b < ctx->blk_counts.size(); ++b) ctx->blk_counts[b] = h[kBlk + b];
@@ -1962,6 +1978,136 @@ int sift_plane_image(sift_ctx* ctx, int kind, int octave, int scale, int mode, d
 int sift_plane_image_device(sift_ctx* ctx, int kind, int octave, int scale, int mode, double coefficient,
                             uint8_t* d_rgba, size_t cap_bytes) {
   return plane_image_common(ctx, kind, octave, scale, mode, coefficient, d_rgba, cap_bytes, false);
+}
+
+// ---- Orientation assignment and descriptors (sift_feature.hip) ------------
+static_assert(sizeof(sift_orientation) == 16 && sizeof(Orientation) == 16, "16-byte orientation records");
+static_assert(kOriBins == SIFT_ORI_BINS && kOriSmooth == SIFT_ORI_SMOOTH && kOriMaxPeaks == SIFT_ORI_MAX_PEAKS &&
+                  kOriLambda == SIFT_ORI_LAMBDA && kOriPeakRatio == SIFT_ORI_PEAK_RATIO,
+              "orientation constants of include/sift_hip.h");
+static_assert(kDescOri == SIFT_DESC_ORI && kDescBytes == SIFT_DESC_BYTES && kDescLambda == SIFT_DESC_LAMBDA &&
+                  kDescCap == SIFT_DESC_CAP && SIFT_DESC_CELLS * SIFT_DESC_CELLS * SIFT_DESC_ORI == SIFT_DESC_BYTES,
+              "descriptor constants of include/sift_hip.h");
+
+// What the two stages need of the context: a settled refinement of one whole
+// image whose keypoints' octaves all have Gaussian planes.
+static int check_features(sift_ctx* ctx) {
+  if (ctx->detect_pending || ctx->begin_pending || !ctx->have_kp)
+    return set_err(ctx, SIFT_E_STATE, "no refinement: run sift_refine or a detection first");
+  if (ctx->P.nimg > 1) return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors of a batch");
+  if (ctx->row0 != 0 || ctx->own_lo >= 0)
+    return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors with a row origin or owned rows");
+  if (ctx->planes_first > ctx->o_first)
+    return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors of a seed-range detection");
+  if (!ctx->have_gauss) return set_err(ctx, SIFT_E_STATE, "Gaussian planes not materialised");
+  for (auto& e : ctx->ev_f)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(ctx->hfeat.ensure(2 * sizeof(unsigned)));
+  return SIFT_OK;
+}
+
+int sift_orient(sift_ctx* ctx, sift_orientation* out, size_t cap, size_t* n_out) {
+  if (!ctx) return SIFT_E_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = check_features(ctx)) return rc;
+  if (!ctx->have_ori) {
+    const int n = (int)ctx->n_kp;
+    ctx->have_desc = false;
+    ctx->n_ori = 0;
+    ctx->orient_ms = 0;
+    if (n > 0) {
+      HIPCHK(ctx->ori_count.ensure((size_t)(n + 1) * sizeof(unsigned)));
+      HIPCHK(ctx->ori_off.ensure((size_t)(n + 1) * sizeof(unsigned)));
+      HIPCHK(ctx->ori_mask.ensure((size_t)n * sizeof(unsigned long long)));
+      HIPCHK(ctx->ori_theta.ensure((size_t)n * kOriMaxPeaks * sizeof(double)));
+      unsigned* h_n = (unsigned*)ctx->hfeat.p;
+      HIPCHK(hipEventRecord(ctx->ev_f[0], ctx->stream));
+      HIPCHK(launch_orient(ctx->P, ctx->gauss.as<float>(), ctx->planes_first, ctx->kp.as<Keypoint>(), n,
+                           ctx->ori_count.as<unsigned>(), ctx->ori_mask.as<unsigned long long>(),
+                           ctx->ori_theta.as<double>(), ctx->stream));
+      HIPCHK(exclusive_sum(ctx, ctx->ori_count.as<unsigned>(), ctx->ori_off.as<unsigned>(), n + 1));
+      HIPCHK(hipMemcpyAsync(h_n, ctx->ori_off.as<unsigned>() + n, sizeof(unsigned), hipMemcpyDeviceToHost,
+                            ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));  // the record count sizes the record buffer
+      const unsigned total = *h_n;
+      HIPCHK(ctx->ori.ensure((size_t)std::max(total, 1u) * sizeof(Orientation)));
+      HIPCHK(launch_orient_emit(ctx->ori_off.as<unsigned>(), ctx->ori_mask.as<unsigned long long>(),
+                                ctx->ori_theta.as<double>(), n, total, ctx->ori.as<Orientation>(), ctx->stream));
+      HIPCHK(hipEventRecord(ctx->ev_f[1], ctx->stream));
+      HIPCHK(hipEventSynchronize(ctx->ev_f[1]));
+      float t = 0;
+      if (hipEventElapsedTime(&t, ctx->ev_f[0], ctx->ev_f[1]) == hipSuccess) ctx->orient_ms = t;
+      ctx->n_ori = total;
+    }
+    ctx->have_ori = true;
+  }
+  if (n_out) *n_out = ctx->n_ori;
+  if (!out) return SIFT_OK;
+  if (cap < ctx->n_ori) return set_err(ctx, SIFT_E_CAPACITY, "orientation buffer too small");
+  if (ctx->n_ori) {
+    HIPCHK(hipMemcpyAsync(out, ctx->ori.p, ctx->n_ori * sizeof(sift_orientation), hipMemcpyDeviceToHost,
+                          ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  return SIFT_OK;
+}
+
+int sift_describe(sift_ctx* ctx, uint8_t* desc, uint8_t* described, size_t cap, size_t* n_out, size_t* n_described) {
+  if (!ctx) return SIFT_E_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = check_features(ctx)) return rc;
+  if (!ctx->have_ori) return set_err(ctx, SIFT_E_STATE, "no orientations: run sift_orient first");
+  const size_t n = ctx->n_ori;
+  if (!ctx->have_desc) {
+    ctx->n_desc_ok = 0;
+    ctx->describe_ms = 0;
+    if (n > 0) {
+      HIPCHK(ctx->desc.ensure(n * kDescBytes));
+      HIPCHK(ctx->desc_ok.ensure(n));
+      HIPCHK(ctx->desc_n.ensure(sizeof(unsigned)));
+      unsigned* h_n = (unsigned*)ctx->hfeat.p + 1;
+      HIPCHK(hipEventRecord(ctx->ev_f[2], ctx->stream));
+      HIPCHK(hipMemsetAsync(ctx->desc_n.p, 0, sizeof(unsigned), ctx->stream));
+      HIPCHK(launch_describe(ctx->P, ctx->gauss.as<float>(), ctx->planes_first, ctx->kp.as<Keypoint>(),
+                             ctx->ori.as<Orientation>(), (int)n, ctx->desc.as<unsigned char>(),
+                             ctx->desc_ok.as<unsigned char>(), ctx->desc_n.as<unsigned>(), ctx->stream));
+      HIPCHK(hipEventRecord(ctx->ev_f[3], ctx->stream));
+      HIPCHK(hipMemcpyAsync(h_n, ctx->desc_n.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+      HIPCHK(hipStreamSynchronize(ctx->stream));
+      float t = 0;
+      if (hipEventElapsedTime(&t, ctx->ev_f[2], ctx->ev_f[3]) == hipSuccess) ctx->describe_ms = t;
+      ctx->n_desc_ok = *h_n;
+    }
+    ctx->have_desc = true;
+  }
+  if (n_out) *n_out = n;
+  if (n_described) *n_described = ctx->n_desc_ok;
+  if (!desc) return described ? set_err(ctx, SIFT_E_ARG, "described without desc") : SIFT_OK;
+  if (cap < n) return set_err(ctx, SIFT_E_CAPACITY, "descriptor buffer too small");
+  if (n) {
+    HIPCHK(d2h_staged(ctx, desc, ctx->desc.p, n * kDescBytes));
+    if (described) HIPCHK(d2h_staged(ctx, described, ctx->desc_ok.p, n));
+  }
+  return SIFT_OK;
+}
+
+int sift_device_features(sift_ctx* ctx, const sift_orientation** d_ori, const uint8_t** d_desc,
+                         const uint8_t** d_described, size_t* n) {
+  if (!ctx || !n) return SIFT_E_ARG;
+  if (!ctx->have_kp || !ctx->have_ori || !ctx->have_desc)
+    return set_err(ctx, SIFT_E_STATE, "no features: run sift_orient and sift_describe first");
+  if (d_ori) *d_ori = ctx->ori.as<const sift_orientation>();
+  if (d_desc) *d_desc = ctx->desc.as<const uint8_t>();
+  if (d_described) *d_described = ctx->desc_ok.as<const uint8_t>();
+  *n = ctx->n_ori;
+  return SIFT_OK;
+}
+
+int sift_last_feature_timings(sift_ctx* ctx, double* orient_ms, double* describe_ms) {
+  if (!ctx) return SIFT_E_ARG;
+  if (orient_ms) *orient_ms = ctx->orient_ms;
+  if (describe_ms) *describe_ms = ctx->describe_ms;
+  return SIFT_OK;
 }
 
 int sift_set_flags(sift_ctx* ctx, int flags) {

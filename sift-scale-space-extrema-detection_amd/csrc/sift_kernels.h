@@ -302,6 +302,31 @@ hipError_t launch_kp_soa(const Keypoint* kp, int n, int32_t* ints, double* reals
 // keys -> 4 int32 per keypoint: octave, scale, whole-image octave row (row0 applied), x.
 hipError_t launch_decode_origins(const Pyramid& P, const unsigned* keys, int n, int32_t* out, hipStream_t st);
 
+// Orientation assignment and descriptors (sift_feature.hip).  The constants
+// are the SIFT_ORI_* / SIFT_DESC_* of include/sift_hip.h (sift_api.hip
+// asserts the match).
+constexpr int kOriBins = 36, kOriSmooth = 6, kOriMaxPeaks = 18;
+constexpr double kOriLambda = 1.5, kOriPeakRatio = 0.8;
+constexpr int kDescOri = 8, kDescBytes = 128;
+constexpr double kDescLambda = 6.0, kDescCap = 0.2;
+// Device twin of sift_orientation, same 16-byte layout.
+struct Orientation {
+  int32_t keypoint, bin;
+  double theta;
+};
+// One wave per keypoint i < n of planes gauss (the pyramid's fp32 Gaussian
+// planes): count[i] = its peaks (count[n] = 0), mask[i] = their bins, theta[18
+// i + j] = the angle of its j-th peak in bin order.
+hipError_t launch_orient(const Pyramid& P, const float* gauss, int planes_first, const Keypoint* kp, int n,
+                         unsigned* count, unsigned long long* mask, double* theta, hipStream_t st);
+// off = the exclusive scan of count: keypoint i's records at out[off[i] ..], ascending bin (cap slots).
+hipError_t launch_orient_emit(const unsigned* off, const unsigned long long* mask, const double* theta, int n,
+                              unsigned cap, Orientation* out, hipStream_t st);
+// One wave per record: desc[128 r ..], described[r]; *n_described (zeroed by the caller) counts the described.
+hipError_t launch_describe(const Pyramid& P, const float* gauss, int planes_first, const Keypoint* kp,
+                           const Orientation* ori, int n, unsigned char* desc, unsigned char* described,
+                           unsigned* n_described, hipStream_t st);
+
 // Image products either side of the path (sift_image.hip).
 // gray/alpha rows are dense (w floats); alpha may be nullptr.
 hipError_t launch_rgba_to_gray(const unsigned char* rgba, size_t stride_bytes, int w, int h, float* gray,

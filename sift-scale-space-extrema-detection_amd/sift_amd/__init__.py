@@ -59,6 +59,7 @@ ABI_SYMBOLS = (
     "sift_detect_from_seed_range_device", "sift_merge_keypoint_blocks_device", "sift_set_owned_rows",
     "sift_last_block_counts", "sift_copy_low_contrast", "sift_set_flags",
     "sift_detect_batch_device", "sift_detect_batch_device_async", "sift_detect_batch",
+    "sift_orient", "sift_describe", "sift_device_features", "sift_last_feature_timings",
 )
 
 
@@ -105,6 +106,9 @@ EXTREMUM_DTYPE = np.dtype([("octave", "<i4"), ("scale", "<i4"), ("x", "<i4"), ("
 KEYPOINT_DTYPE = np.dtype([("octave", "<i4"), ("scale_level", "<i4"), ("local_x", "<i4"),
                            ("local_y", "<i4"), ("abs_x", "<f8"), ("abs_y", "<f8"),
                            ("abs_sigma", "<f8"), ("interp_value", "<f8")])
+
+ORIENTATION_DTYPE = np.dtype([("keypoint", "<i4"), ("bin", "<i4"), ("theta", "<f8")])
+DESC_BYTES = 128
 
 _lib = None
 
@@ -195,6 +199,10 @@ def lib():
                                             ctypes.c_double, vp, sz]),
         "sift_plane_image_device": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_double, vp, sz]),
+        "sift_orient": (ctypes.c_int, [vp, vp, sz, szp]),
+        "sift_describe": (ctypes.c_int, [vp, vp, vp, sz, szp, szp]),
+        "sift_device_features": (ctypes.c_int, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), szp]),
+        "sift_last_feature_timings": (ctypes.c_int, [vp, dp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -672,6 +680,44 @@ class Context:
         buf = ctypes.create_string_buffer(n.value + 1)
         self._check(self._L.sift_last_pass_kernels(self._h, buf, n.value + 1, ctypes.byref(n)), "sift_last_pass_kernels")
         return buf.value.decode()
+
+    # -- orientation assignment and descriptors ------------------------------
+    def orient(self):
+        """Reference orientations of the last keypoints (sift_orient): a
+        structured array (keypoint, bin, theta), keypoint order then bin."""
+        n = ctypes.c_size_t()
+        self._check(self._L.sift_orient(self._h, None, 0, ctypes.byref(n)), "sift_orient")
+        out = np.zeros(max(n.value, 1), dtype=ORIENTATION_DTYPE)
+        self._check(self._L.sift_orient(self._h, out.ctypes.data_as(ctypes.c_void_p), out.shape[0], ctypes.byref(n)),
+                    "sift_orient")
+        return out[:n.value]
+
+    def describe(self):
+        """Descriptors of the last orient()'s records (sift_describe):
+        (uint8 [n, 128], bool [n] described)."""
+        n, nd = ctypes.c_size_t(), ctypes.c_size_t()
+        self._check(self._L.sift_describe(self._h, None, None, 0, ctypes.byref(n), ctypes.byref(nd)), "sift_describe")
+        desc = np.zeros((max(n.value, 1), DESC_BYTES), dtype=np.uint8)
+        ok = np.zeros(max(n.value, 1), dtype=np.uint8)
+        self._check(self._L.sift_describe(self._h, desc.ctypes.data_as(ctypes.c_void_p),
+                                          ok.ctypes.data_as(ctypes.c_void_p), desc.shape[0], ctypes.byref(n),
+                                          ctypes.byref(nd)), "sift_describe")
+        return desc[:n.value], ok[:n.value].astype(bool)
+
+    def device_features(self):
+        """Device pointers of the last orient() + describe():
+        (d_orientations, d_descriptors, d_described, n)."""
+        po, pd, pk, n = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._L.sift_device_features(self._h, ctypes.byref(po), ctypes.byref(pd), ctypes.byref(pk),
+                                                 ctypes.byref(n)), "sift_device_features")
+        return po.value or 0, pd.value or 0, pk.value or 0, n.value
+
+    def feature_timings(self):
+        """Device ms of the last orient() and describe()."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        self._check(self._L.sift_last_feature_timings(self._h, ctypes.byref(a), ctypes.byref(b)),
+                    "sift_last_feature_timings")
+        return dict(orient_ms=a.value, describe_ms=b.value)
 
     def stream(self):
         return self._L.sift_stream(self._h)
