@@ -492,6 +492,30 @@ int sift_device_features(struct sift_ctx *ctx, const sift_orientation **d_ori, c
  * sift_describe, milliseconds. */
 int sift_last_feature_timings(struct sift_ctx *ctx, double *orient_ms, double *describe_ms);
 
+/* Use caller-supplied keypoints for the stages that follow (sift_orient,
+ * sift_describe, sift_copy_keypoints), as sift_set_candidates does for the
+ * refinement; detected by symbol like the entry points above.  Needs a
+ * single-image pyramid with materialised Gaussian planes and no row origin or
+ * owned rows (else SIFT_E_STATE / SIFT_E_UNSUPPORTED as sift_orient returns
+ * them); no refinement is needed.  Each record's octave must have planes and
+ * its scale_level lie in [0, scales_per_octave + 3), and n must be below
+ * 2^31 - 1: else SIFT_E_ARG and the previous list stays.  Coordinates and
+ * sigma are taken as they are: a keypoint whose box is not inside its plane
+ * (NaN, infinite, non-positive sigma included) simply has no record.  Drops
+ * the orientations and descriptors of the previous list, and resets what the
+ * replaced refinement left behind rather than serving it stale: the singular
+ * count and refine_ms read 0, sift_last_block_counts reports no blocks and the
+ * keypoint origins return SIFT_E_STATE until the next refinement. */
+int sift_set_keypoints(struct sift_ctx *ctx, const sift_keypoint *kp, size_t n);
+
+/* Use caller-supplied orientation records (in the caller's order) for the next
+ * sift_describe; sift_orient afterwards copies them back without recomputing.
+ * Needs keypoints (a refinement or sift_set_keypoints).  Every record must
+ * have 0 <= keypoint < the keypoint count, 0 <= bin < SIFT_ORI_BINS and a
+ * finite theta in [0, 2 pi): else SIFT_E_ARG and the previous records stay.
+ * Drops the descriptors of the previous records. */
+int sift_set_orientations(struct sift_ctx *ctx, const sift_orientation *rec, size_t n);
+
 /* Wait for all work queued on ctx's stream. */
 int sift_synchronize(struct sift_ctx *ctx);
 

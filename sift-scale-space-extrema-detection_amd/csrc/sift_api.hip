@@ -1989,17 +1989,26 @@ static_assert(kDescOri == SIFT_DESC_ORI && kDescBytes == SIFT_DESC_BYTES && kDes
                   kDescCap == SIFT_DESC_CAP && SIFT_DESC_CELLS * SIFT_DESC_CELLS * SIFT_DESC_ORI == SIFT_DESC_BYTES,
               "descriptor constants of include/sift_hip.h");
 
-// What the two stages need of the context: a settled refinement of one whole
-// image whose keypoints' octaves all have Gaussian planes.
-static int check_features(sift_ctx* ctx) {
-  if (ctx->detect_pending || ctx->begin_pending || !ctx->have_kp)
-    return set_err(ctx, SIFT_E_STATE, "no refinement: run sift_refine or a detection first");
+// What the two stages need of the pyramid, whoever supplies the keypoints
+// (sift_set_keypoints needs no more): one whole image whose octaves all have
+// Gaussian planes.
+static int check_feature_planes(sift_ctx* ctx) {
+  if (ctx->detect_pending || ctx->begin_pending || ctx->dog_source == kNone)
+    return set_err(ctx, SIFT_E_STATE, "no pyramid: build or load one first");
   if (ctx->P.nimg > 1) return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors of a batch");
   if (ctx->row0 != 0 || ctx->own_lo >= 0)
     return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors with a row origin or owned rows");
   if (ctx->planes_first > ctx->o_first)
     return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors of a seed-range detection");
   if (!ctx->have_gauss) return set_err(ctx, SIFT_E_STATE, "Gaussian planes not materialised");
+  return SIFT_OK;
+}
+
+// ... and of the context: a settled refinement (or sift_set_keypoints) on that pyramid.
+static int check_features(sift_ctx* ctx) {
+  if (ctx->detect_pending || ctx->begin_pending || !ctx->have_kp)
+    return set_err(ctx, SIFT_E_STATE, "no refinement: run sift_refine or a detection first");
+  if (int rc = check_feature_planes(ctx)) return rc;
   for (auto& e : ctx->ev_f)
     if (!e) HIPCHK(hipEventCreate(&e));
   HIPCHK(ctx->hfeat.ensure(2 * sizeof(unsigned)));
@@ -2107,6 +2116,61 @@ int sift_last_feature_timings(sift_ctx* ctx, double* orient_ms, double* describe
   if (!ctx) return SIFT_E_ARG;
   if (orient_ms) *orient_ms = ctx->orient_ms;
   if (describe_ms) *describe_ms = ctx->describe_ms;
+  return SIFT_OK;
+}
+
+int sift_set_keypoints(sift_ctx* ctx, const sift_keypoint* kp, size_t n) {
+  if (!ctx || (!kp && n)) return SIFT_E_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = check_feature_planes(ctx)) return rc;
+  if (n >= (size_t)0x7fffffff) return set_err(ctx, SIFT_E_ARG, "too many keypoints");  // the scan runs over n + 1
+  const Pyramid& P = ctx->P;
+  for (size_t i = 0; i < n; ++i) {
+    if (kp[i].octave < ctx->planes_first || kp[i].octave >= P.O)
+      return set_err(ctx, SIFT_E_ARG, "keypoint octave out of range");
+    if (kp[i].scale_level < 0 || kp[i].scale_level >= P.NS)
+      return set_err(ctx, SIFT_E_ARG, "keypoint scale_level out of range");
+  }
+  HIPCHK(ctx->kp.ensure(std::max<size_t>(n, 1) * sizeof(Keypoint)));
+  if (n) {
+    HIPCHK(hipMemcpyAsync(ctx->kp.p, kp, n * sizeof(sift_keypoint), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  ctx->n_kp = n;
+  ctx->have_kp = true;
+  ctx->have_ori = ctx->have_desc = false;
+  ctx->n_ori = ctx->n_desc_ok = 0;
+  // nothing of the refinement this list replaces is served afterwards
+  ctx->n_sing = 0;
+  ctx->has_origins = false;
+  ctx->blk_counts.clear();
+  ctx->tm.refine_ms = 0;
+  ctx->orient_ms = ctx->describe_ms = 0;
+  return SIFT_OK;
+}
+
+int sift_set_orientations(sift_ctx* ctx, const sift_orientation* rec, size_t n) {
+  if (!ctx || (!rec && n)) return SIFT_E_ARG;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = check_features(ctx)) return rc;
+  if (n > (size_t)0x7fffffff) return set_err(ctx, SIFT_E_ARG, "too many orientation records");
+  for (size_t i = 0; i < n; ++i) {
+    if (rec[i].keypoint < 0 || (size_t)rec[i].keypoint >= ctx->n_kp)
+      return set_err(ctx, SIFT_E_ARG, "orientation record of no keypoint");
+    if (rec[i].bin < 0 || rec[i].bin >= kOriBins) return set_err(ctx, SIFT_E_ARG, "orientation bin out of range");
+    if (!(rec[i].theta >= 0.0 && rec[i].theta < 2.0 * M_PI))  // a NaN fails both
+      return set_err(ctx, SIFT_E_ARG, "theta outside [0, 2 pi)");
+  }
+  HIPCHK(ctx->ori.ensure(std::max<size_t>(n, 1) * sizeof(Orientation)));
+  if (n) {
+    HIPCHK(hipMemcpyAsync(ctx->ori.p, rec, n * sizeof(sift_orientation), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+  }
+  ctx->n_ori = n;
+  ctx->have_ori = true;
+  ctx->have_desc = false;
+  ctx->n_desc_ok = 0;
+  ctx->orient_ms = ctx->describe_ms = 0;
   return SIFT_OK;
 }
 

@@ -60,6 +60,7 @@ ABI_SYMBOLS = (
     "sift_last_block_counts", "sift_copy_low_contrast", "sift_set_flags",
     "sift_detect_batch_device", "sift_detect_batch_device_async", "sift_detect_batch",
     "sift_orient", "sift_describe", "sift_device_features", "sift_last_feature_timings",
+    "sift_set_keypoints", "sift_set_orientations",
 )
 
 
@@ -203,6 +204,8 @@ def lib():
         "sift_describe": (ctypes.c_int, [vp, vp, vp, sz, szp, szp]),
         "sift_device_features": (ctypes.c_int, [vp, ctypes.POINTER(vp), ctypes.POINTER(vp), ctypes.POINTER(vp), szp]),
         "sift_last_feature_timings": (ctypes.c_int, [vp, dp, dp]),
+        "sift_set_keypoints": (ctypes.c_int, [vp, vp, sz]),
+        "sift_set_orientations": (ctypes.c_int, [vp, vp, sz]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -703,6 +706,18 @@ class Context:
                                           ok.ctypes.data_as(ctypes.c_void_p), desc.shape[0], ctypes.byref(n),
                                           ctypes.byref(nd)), "sift_describe")
         return desc[:n.value], ok[:n.value].astype(bool)
+
+    def set_keypoints(self, kp):
+        """Caller keypoints (KEYPOINT_DTYPE) for orient() / describe() / keypoints() (sift_set_keypoints)."""
+        k = np.ascontiguousarray(kp, dtype=KEYPOINT_DTYPE)
+        self._check(self._L.sift_set_keypoints(self._h, k.ctypes.data_as(ctypes.c_void_p), k.shape[0]),
+                    "sift_set_keypoints")
+
+    def set_orientations(self, recs):
+        """Caller orientation records (ORIENTATION_DTYPE, any order) for describe() (sift_set_orientations)."""
+        r = np.ascontiguousarray(recs, dtype=ORIENTATION_DTYPE)
+        self._check(self._L.sift_set_orientations(self._h, r.ctypes.data_as(ctypes.c_void_p), r.shape[0]),
+                    "sift_set_orientations")
 
     def device_features(self):
         """Device pointers of the last orient() + describe():

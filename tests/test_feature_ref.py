@@ -2,34 +2,12 @@
 (tests/feature_ref.py) against properties it cannot pass by accident, and the
 binding's side of the new entry points.  No GPU."""
 import numpy as np
+import pytest
 
+import feature_cases as fc
 import feature_ref as fr
 import sift_amd
-
-
-def keypoints_at(points, octave=1, scale=1):
-    """KEYPOINT_DTYPE records at octave-local (x, y, sigma) of octave `octave` (delta = 2^(octave-1))."""
-    delta = 2.0 ** (octave - 1)
-    kp = np.zeros(len(points), dtype=sift_amd.KEYPOINT_DTYPE)
-    for i, (x, y, sg) in enumerate(points):
-        kp[i] = (octave, scale, int(round(x)), int(round(y)), x * delta, y * delta, sg * delta, 0.0)
-    return kp
-
-
-def ramp(a, b, h=64, w=64):
-    v, u = np.mgrid[0:h, 0:w]
-    return (a * u + b * v).astype(np.float32)
-
-
-def smooth_plane(h, w, seed):
-    """A smooth fp32 plane with gradients of every direction: random low-frequency waves."""
-    rng = np.random.RandomState(seed)
-    v, u = np.mgrid[0:h, 0:w].astype(np.float64)
-    P = np.zeros((h, w))
-    for _ in range(24):
-        fx, fy = rng.uniform(-0.25, 0.25, 2)
-        P += rng.uniform(0.2, 1.0) * np.sin(fx * u + fy * v + rng.uniform(0, 2 * np.pi))
-    return (P / 8.0).astype(np.float32)
+from feature_cases import keypoints_at, ramp, smooth_plane
 
 
 def test_binding_declares_the_feature_entry_points():
@@ -141,3 +119,60 @@ def test_descriptor_is_normalised_and_capped():
     nrm = np.sqrt((f * f).sum(axis=1))
     assert ((nrm > 0.9) & (nrm <= 1.0)).all()
     assert desc.max() <= 255
+
+
+def test_binding_declares_the_keypoint_and_orientation_seams():
+    L = sift_amd.lib()
+    for name in ("sift_set_keypoints", "sift_set_orientations"):
+        assert hasattr(L, name), name
+        assert name in sift_amd.ABI_SYMBOLS
+    for method in ("set_keypoints", "set_orientations"):
+        assert callable(getattr(sift_amd.Context, method))
+
+
+@pytest.mark.parametrize("name", sorted(fc.CASES))
+def test_edge_cases_give_their_counts_within_the_flag_caps(name):
+    """Every case of tests/feature_cases.py on the reference alone: the exact
+    counts written next to it, and ambiguity flags within the caps of
+    tests/test_gpu_features.py (1 % of the keypoints, 0.1 % of the bytes --
+    none at all below 100 keypoints / 1000 bytes)."""
+    c, ref = fc.case(name), fc.reference(name)
+    got = fc.counts_of(c["kp"], ref)
+    print("case %s: %d keypoints; records, no record, multi-peak, described, bytes at 255 = %s; "
+          "%d flagged keypoints, %d flagged bytes" % (name, len(c["kp"]), got, int(ref["amb"].sum()),
+                                                      int(ref["flag"].sum())))
+    assert got == c["counts"]
+    assert ref["amb"].sum() <= 0.01 * len(c["kp"])
+    assert ref["flag"].sum() <= 0.001 * ref["flag"].size
+    assert not ref["desc"][~ref["described"]].any()
+
+
+def test_edge_case_properties_hold_on_the_reference():
+    """What tests/test_gpu_feature_edges.py relies on beyond the counts."""
+    for name, first in (("a0", 0), ("a1", 6)):
+        c, ref = fc.case(name), fc.reference(name)
+        want = np.array([fc.RAMP_BINS[i] for i in fc.ramp_slots(first)] * fc.O)
+        assert (ref["ori"]["keypoint"] == np.arange(len(want))).all() and (ref["ori"]["bin"] == want).all()
+        assert np.abs(ref["ori"]["theta"] - want * np.pi / 18).max() < 1e-9
+        diagonal = want % 9 != 0
+        assert ((ref["desc"][diagonal] > 0).sum(axis=1) == 32).all() and (ref["desc"][diagonal].max(axis=1) == 128).all()
+    c, ref = fc.case("b"), fc.reference("b")
+    assert (np.bincount(ref["ori"]["keypoint"], minlength=len(c["kp"])) == fc.BORDER_HAS_RECORD).all()
+    x = c["kp"]["abs_x"] / 2.0 ** (c["kp"]["octave"] - 1.0)
+    assert (ref["described"] == (x[ref["ori"]["keypoint"]] == 22.0)).all()
+    # degenerate gradients, with theta = 0 supplied: constant planes are described with zero bytes, the step
+    # saturates exactly four
+    c, recs = fc.case("c"), fc.degenerate_records()
+    desc, described, flag = fr.describe(c["planes"], c["kp"], recs)
+    assert described.all() and not desc[:fc.STEP_KEYPOINT].any() and not flag[:fc.STEP_KEYPOINT].any()
+    assert np.nonzero(desc[fc.STEP_KEYPOINT])[0].tolist() == fc.STEP_BYTES
+    assert (desc[fc.STEP_KEYPOINT][fc.STEP_BYTES] == 255).all()
+    assert np.nonzero(flag[fc.STEP_KEYPOINT])[0].tolist() == fc.STEP_BYTES  # q = 256 exactly
+    c, ref = fc.case("d"), fc.reference("d")
+    octave = c["kp"]["octave"][ref["ori"]["keypoint"]]
+    assert [int(ref["described"][octave == o].sum()) for o in range(fc.O)] == [79, 31, 27]
+    assert np.bincount(ref["ori"]["keypoint"]).max() == 2
+    ref = fc.reference("g")
+    assert (np.diff(ref["ori"]["bin"]) > 0).all() and len(ref["ori"]) == 4
+    idx, distinct = fc.many_from(fc.reference("d"))
+    assert len(idx) == fc.H_COUNT and len(set(idx.tolist())) == len(distinct) == 50
