@@ -516,6 +516,77 @@ int sift_set_keypoints(struct sift_ctx *ctx, const sift_keypoint *kp, size_t n);
  * Drops the descriptors of the previous records. */
 int sift_set_orientations(struct sift_ctx *ctx, const sift_orientation *rec, size_t n);
 
+/* ---- Brute-force descriptor matching ---------------------------------------
+ *
+ * Descriptors are rows of SIFT_DESC_BYTES (128) uint8.  For query row q and
+ * train row t the squared L2 distance is d2(q, t) = sum_k (Q[q][k] - T[t][k])^2,
+ * an integer in [0, 128 * 255^2 = 8323200].  A row may be masked out by a
+ * `described`-style byte array (0 = the row does not take part; sift_describe
+ * writes zero bytes for undescribed rows); a NULL mask means every row takes
+ * part.  For every query row the stage returns the two smallest (d2, t) pairs
+ * over the unmasked train rows in lexicographic order (d2, then train index):
+ * among equal distances the lowest index wins, and `second` may be at the same
+ * distance as `best`.  A missing neighbour has index -1 and d2 =
+ * SIFT_MATCH_NONE_D2: both for a masked query row or no unmasked train row,
+ * `second` alone for exactly one unmasked train row.  The arithmetic is
+ * integer (int8 matrix cores): results are exact and do not depend on how the
+ * work is split.  Like the feature stages, these entry points are detected by
+ * symbol; SIFT_ABI_VERSION stays 9. */
+struct sift_match {
+  int32_t best, second, d2_best, d2_second;
+}; /* 16 bytes; a struct tag, as stat(2)'s: C has one namespace for typedefs and functions, and the
+      host entry point below is sift_match too */
+#define SIFT_MATCH_NONE_D2 INT32_MAX
+
+/* One accepted pair of the selection below. */
+typedef struct {
+  int32_t query, train, d2, d2_second;
+} sift_match_pair; /* 16 bytes */
+
+/* Everything in device memory of ctx's device: n_query x 128 and n_train x 128
+ * descriptor bytes (16-byte aligned), their masks (n bytes each, or NULL) and
+ * d_out for n_query records.  Ordered on ctx's stream, complete on return.
+ * Counts must be below 2^31 - 1 and pointers non-NULL for non-zero counts, else
+ * SIFT_E_ARG with nothing written; a zero count is valid (n_train == 0: every
+ * neighbour missing). */
+int sift_match_device(struct sift_ctx *ctx, const uint8_t *d_query, const uint8_t *d_query_mask, size_t n_query,
+                      const uint8_t *d_train, const uint8_t *d_train_mask, size_t n_train, struct sift_match *d_out);
+/* The same with host buffers, through the context's own device buffers. */
+int sift_match(struct sift_ctx *ctx, const uint8_t *query, const uint8_t *query_mask, size_t n_query,
+               const uint8_t *train, const uint8_t *train_mask, size_t n_train, struct sift_match *out);
+
+/* Query = the last sift_describe of ctx, train = that of train_ctx on the same
+ * device (it may be ctx itself); the masks are their `described` arrays.  The
+ * records stay on the device when out == NULL (*n_out still returned;
+ * sift_device_matches).  SIFT_E_STATE without a describe on either side;
+ * SIFT_E_CAPACITY: *n_out = required count, nothing written. */
+int sift_match_features(struct sift_ctx *ctx, struct sift_ctx *train_ctx, struct sift_match *out, size_t cap, size_t *n_out);
+
+/* Device pointer of the last sift_match / sift_match_features records of ctx
+ * (valid until its next match). */
+int sift_device_matches(struct sift_ctx *ctx, const struct sift_match **d_match, size_t *n);
+
+/* The ordered, compacted list of accepted pairs of d_fwd (n_query records of a
+ * query -> train match), ascending query index.  Query q is accepted when
+ *   best >= 0, and
+ *   ratio <= 0 (no ratio test), or second < 0, or
+ *     (double)d2_best < (ratio * ratio) * (double)d2_second   (fp64, no contraction), and
+ *   d_rev == NULL, or best < n_train and d_rev[best].best == q   (d_rev: the
+ *     n_train records of the swapped, train -> query match: a mutual check).
+ * ratio must be finite and < 1, or <= 0: else SIFT_E_ARG.  *n_out = accepted
+ * pairs; d_pairs == NULL only counts; SIFT_E_CAPACITY when cap < *n_out, nothing
+ * written.  Device memory of ctx's device; complete on return.  _host: the
+ * same with host arrays. */
+int sift_match_select(struct sift_ctx *ctx, const struct sift_match *d_fwd, size_t n_query, const struct sift_match *d_rev,
+                      size_t n_train, double ratio, sift_match_pair *d_pairs, size_t cap, size_t *n_out);
+int sift_match_select_host(struct sift_ctx *ctx, const struct sift_match *fwd, size_t n_query, const struct sift_match *rev,
+                           size_t n_train, double ratio, sift_match_pair *pairs, size_t cap, size_t *n_out);
+
+/* Device time of the last match (row preparation, match, split merge) and of
+ * the last selection (flags, scan, count read-back, and the emission when pairs
+ * were written), milliseconds. */
+int sift_last_match_timings(struct sift_ctx *ctx, double *match_ms, double *select_ms);
+
 /* Wait for all work queued on ctx's stream. */
 int sift_synchronize(struct sift_ctx *ctx);
 

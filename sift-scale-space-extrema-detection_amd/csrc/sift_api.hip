@@ -142,6 +142,9 @@ enum DogSource { kNone = 0, kNative = 1, kForeign = 2 };
 constexpr int kBlk = 64;
 constexpr int kCntAll = kBlk + kBlkWords;  // per-block counts, block starts, order flag (sift_kernels.h)
 
+// Slots of the pinned count read-backs of the feature and matching stages (sift_ctx::hfeat).
+enum { kFeatOri = 0, kFeatDesc = 1, kFeatPairs = 2, kFeatSlots = 3 };
+
 }  // namespace
 
 struct sift_ctx {
@@ -223,9 +226,18 @@ struct sift_ctx {
   size_t n_ori = 0, n_desc_ok = 0;             // records, described records
   DBuf ori_count, ori_off, ori_mask, ori_theta;  // per keypoint: peaks, their exclusive scan, bins, angles
   DBuf ori, desc, desc_ok, desc_n;             // records, 128 bytes each, described flags, described count
-  HBuf hfeat;                                  // pinned: the two counts
+  HBuf hfeat;                                  // pinned: kFeatSlots count read-backs (kFeatOri ..)
   hipEvent_t ev_f[4]{};                        // around the orientation stage [0, 1] and the descriptor stage [2, 3]
   double orient_ms = 0, describe_ms = 0;
+  // descriptor matching (sift_match.hip)
+  DBuf m_qs, m_ts, m_qn, m_kb;                 // shifted, padded query / train rows; query norms, train key bases
+  DBuf m_part, m_out;                          // per-split partial records; the last match's records
+  DBuf m_in_q, m_in_t, m_in_qm, m_in_tm;       // host-form inputs (sift_match)
+  DBuf m_fwd, m_rev, m_flag, m_off, m_pairs;   // selection: host-form inputs, flags, their scan, host-form pairs
+  size_t n_match = 0;                          // records in m_out
+  bool have_match = false;
+  hipEvent_t ev_m[4]{};                        // around the match [0, 1] and the selection [2, 3]
+  double match_ms = 0, select_ms = 0;
   DBuf counters, temp;
   DBuf rgba, alpha, display, mm_parts;         // image products (sift_image.hip)
   unsigned* h_counters = nullptr;              // pinned mirror of counters (+ per-block keypoint counts at kBlk)
@@ -249,6 +261,8 @@ struct sift_ctx {
     for (auto& e : ev_go)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_f)
+      if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_m)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_pl)
       if (e) (void)hipEventDestroy(e);
@@ -2011,7 +2025,7 @@ static int check_features(sift_ctx* ctx) {
   if (int rc = check_feature_planes(ctx)) return rc;
   for (auto& e : ctx->ev_f)
     if (!e) HIPCHK(hipEventCreate(&e));
-  HIPCHK(ctx->hfeat.ensure(2 * sizeof(unsigned)));
+  HIPCHK(ctx->hfeat.ensure(kFeatSlots * sizeof(unsigned)));
   return SIFT_OK;
 }
 
@@ -2029,7 +2043,7 @@ int sift_orient(sift_ctx* ctx, sift_orientation* out, size_t cap, size_t* n_out)
       HIPCHK(ctx->ori_off.ensure((size_t)(n + 1) * sizeof(unsigned)));
       HIPCHK(ctx->ori_mask.ensure((size_t)n * sizeof(unsigned long long)));
       HIPCHK(ctx->ori_theta.ensure((size_t)n * kOriMaxPeaks * sizeof(double)));
-      unsigned* h_n = (unsigned*)ctx->hfeat.p;
+      unsigned* h_n = (unsigned*)ctx->hfeat.p + kFeatOri;
       HIPCHK(hipEventRecord(ctx->ev_f[0], ctx->stream));
       HIPCHK(launch_orient(ctx->P, ctx->gauss.as<float>(), ctx->planes_first, ctx->kp.as<Keypoint>(), n,
                            ctx->ori_count.as<unsigned>(), ctx->ori_mask.as<unsigned long long>(),
@@ -2074,7 +2088,7 @@ int sift_describe(sift_ctx* ctx, uint8_t* desc, uint8_t* described, size_t cap, 
       HIPCHK(ctx->desc.ensure(n * kDescBytes));
       HIPCHK(ctx->desc_ok.ensure(n));
       HIPCHK(ctx->desc_n.ensure(sizeof(unsigned)));
-      unsigned* h_n = (unsigned*)ctx->hfeat.p + 1;
+      unsigned* h_n = (unsigned*)ctx->hfeat.p + kFeatDesc;
       HIPCHK(hipEventRecord(ctx->ev_f[2], ctx->stream));
       HIPCHK(hipMemsetAsync(ctx->desc_n.p, 0, sizeof(unsigned), ctx->stream));
       HIPCHK(launch_describe(ctx->P, ctx->gauss.as<float>(), ctx->planes_first, ctx->kp.as<Keypoint>(),
@@ -2171,6 +2185,231 @@ int sift_set_orientations(sift_ctx* ctx, const sift_orientation* rec, size_t n) 
   ctx->have_desc = false;
   ctx->n_desc_ok = 0;
   ctx->orient_ms = ctx->describe_ms = 0;
+  return SIFT_OK;
+}
+
+// ---- Descriptor matching (sift_match.hip) ---------------------------------
+static_assert(sizeof(struct sift_match) == 16 && sizeof(Match) == 16 && sizeof(sift_match_pair) == 16 &&
+                  sizeof(MatchPair) == 16,
+              "16-byte match records");
+static_assert(SIFT_MATCH_NONE_D2 == INT32_MAX && kDescBytes == SIFT_DESC_BYTES, "match constants of include/sift_hip.h");
+
+static bool match_count_ok(size_t n) { return n < (size_t)0x7fffffff; }
+static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+static int match_events(sift_ctx* ctx) {
+  for (auto& e : ctx->ev_m)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(ctx->hfeat.ensure(kFeatSlots * sizeof(unsigned)));
+  return SIFT_OK;
+}
+
+// The match of validated device arrays into d_out (n_query records), timed and complete on return.
+static int match_run(sift_ctx* ctx, const uint8_t* d_q, const uint8_t* d_qm, int nq, const uint8_t* d_t,
+                     const uint8_t* d_tm, int nt, Match* d_out) {
+  if (int rc = match_events(ctx)) return rc;
+  ctx->match_ms = 0;
+  if (nq == 0) return SIFT_OK;
+  const MatchSplit sp = match_split(nq, nt);
+  Match* part = d_out;
+  if (nt > 0) {
+    const size_t qrows = (size_t)match_query_rows(nq), trows = (size_t)match_train_rows(nt);
+    HIPCHK(ctx->m_qs.ensure(qrows * kDescBytes));
+    HIPCHK(ctx->m_qn.ensure(qrows * sizeof(int)));
+    HIPCHK(ctx->m_ts.ensure(trows * kDescBytes));
+    HIPCHK(ctx->m_kb.ensure(trows * sizeof(int)));
+    if (sp.splits > 1) {
+      HIPCHK(ctx->m_part.ensure((size_t)sp.splits * nq * sizeof(Match)));
+      part = ctx->m_part.as<Match>();
+    }
+    HIPCHK(hipEventRecord(ctx->ev_m[0], ctx->stream));
+    HIPCHK(launch_match_prep(d_q, d_qm, nq, (long long)qrows, 0, ctx->m_qs.as<unsigned char>(), ctx->m_qn.as<int>(),
+                             ctx->stream));
+    HIPCHK(launch_match_prep(d_t, d_tm, nt, (long long)trows, 1, ctx->m_ts.as<unsigned char>(), ctx->m_kb.as<int>(),
+                             ctx->stream));
+    HIPCHK(launch_match(ctx->m_qs.as<unsigned char>(), ctx->m_qn.as<int>(), nq, ctx->m_ts.as<unsigned char>(),
+                        ctx->m_kb.as<int>(), nt, part, ctx->stream));
+    if (sp.splits > 1) HIPCHK(launch_match_merge(part, sp.splits, nq, d_out, ctx->stream));
+  } else {
+    HIPCHK(hipEventRecord(ctx->ev_m[0], ctx->stream));
+    HIPCHK(launch_match_merge(nullptr, 0, nq, d_out, ctx->stream));  // no train rows: every neighbour missing
+  }
+  HIPCHK(hipEventRecord(ctx->ev_m[1], ctx->stream));
+  HIPCHK(hipEventSynchronize(ctx->ev_m[1]));
+  float t = 0;
+  if (hipEventElapsedTime(&t, ctx->ev_m[0], ctx->ev_m[1]) == hipSuccess) ctx->match_ms = t;
+  return SIFT_OK;
+}
+
+int sift_match_device(sift_ctx* ctx, const uint8_t* d_query, const uint8_t* d_query_mask, size_t n_query,
+                      const uint8_t* d_train, const uint8_t* d_train_mask, size_t n_train, struct sift_match* d_out) {
+  if (!ctx) return SIFT_E_ARG;
+  if (!match_count_ok(n_query) || !match_count_ok(n_train)) return set_err(ctx, SIFT_E_ARG, "too many descriptors");
+  if ((n_query && (!d_query || !d_out)) || (n_train && !d_train))
+    return set_err(ctx, SIFT_E_ARG, "null descriptor or result pointer");
+  if (!aligned16(d_query) || !aligned16(d_train)) return set_err(ctx, SIFT_E_ARG, "descriptors not 16-byte aligned");
+  HIPCHK(hipSetDevice(ctx->device));
+  return match_run(ctx, d_query, d_query_mask, (int)n_query, d_train, d_train_mask, (int)n_train,
+                   reinterpret_cast<Match*>(d_out));
+}
+
+// Host bytes into a context buffer (nothing for bytes == 0 or src == nullptr).
+static int match_upload(sift_ctx* ctx, DBuf& b, const void* src, size_t bytes) {
+  if (!src || !bytes) return SIFT_OK;
+  HIPCHK(b.ensure(bytes));
+  HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return SIFT_OK;
+}
+
+int sift_match(sift_ctx* ctx, const uint8_t* query, const uint8_t* query_mask, size_t n_query, const uint8_t* train,
+               const uint8_t* train_mask, size_t n_train, struct sift_match* out) {
+  if (!ctx) return SIFT_E_ARG;
+  if (!match_count_ok(n_query) || !match_count_ok(n_train)) return set_err(ctx, SIFT_E_ARG, "too many descriptors");
+  if ((n_query && (!query || !out)) || (n_train && !train))
+    return set_err(ctx, SIFT_E_ARG, "null descriptor or result pointer");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (n_query == 0) {  // the last match has no records
+    ctx->match_ms = 0;
+    ctx->n_match = 0;
+    ctx->have_match = true;
+    return SIFT_OK;
+  }
+  if (int rc = match_upload(ctx, ctx->m_in_q, query, n_query * kDescBytes)) return rc;
+  if (int rc = match_upload(ctx, ctx->m_in_qm, query_mask, n_query)) return rc;
+  if (int rc = match_upload(ctx, ctx->m_in_t, train, n_train * kDescBytes)) return rc;
+  if (int rc = match_upload(ctx, ctx->m_in_tm, n_train ? train_mask : nullptr, n_train)) return rc;
+  HIPCHK(ctx->m_out.ensure(n_query * sizeof(Match)));
+  ctx->have_match = false;
+  int rc = match_run(ctx, ctx->m_in_q.as<uint8_t>(), query_mask ? ctx->m_in_qm.as<uint8_t>() : nullptr, (int)n_query,
+                     ctx->m_in_t.as<uint8_t>(), n_train && train_mask ? ctx->m_in_tm.as<uint8_t>() : nullptr,
+                     (int)n_train, ctx->m_out.as<Match>());
+  if (rc) return rc;
+  ctx->n_match = n_query;
+  ctx->have_match = true;
+  HIPCHK(d2h_staged(ctx, out, ctx->m_out.p, n_query * sizeof(Match)));
+  return SIFT_OK;
+}
+
+int sift_match_features(sift_ctx* ctx, sift_ctx* train_ctx, struct sift_match* out, size_t cap, size_t* n_out) {
+  if (!ctx || !train_ctx) return SIFT_E_ARG;
+  for (sift_ctx* c : {ctx, train_ctx})
+    if (c->detect_pending || c->begin_pending || !c->have_kp || !c->have_ori || !c->have_desc)
+      return set_err(ctx, SIFT_E_STATE, "no descriptors: run sift_orient and sift_describe on both contexts first");
+  if (ctx->device != train_ctx->device) return set_err(ctx, SIFT_E_ARG, "contexts on different devices");
+  HIPCHK(hipSetDevice(ctx->device));
+  const size_t nq = ctx->n_ori, nt = train_ctx->n_ori;  // both below 2^31 - 1 (sift_orient's scan, sift_set_orientations)
+  if (!match_count_ok(nq) || !match_count_ok(nt)) return set_err(ctx, SIFT_E_ARG, "too many descriptors");
+  HIPCHK(ctx->m_out.ensure(std::max<size_t>(nq, 1) * sizeof(Match)));
+  ctx->have_match = false;
+  int rc = match_run(ctx, ctx->desc.as<uint8_t>(), ctx->desc_ok.as<uint8_t>(), (int)nq, train_ctx->desc.as<uint8_t>(),
+                     train_ctx->desc_ok.as<uint8_t>(), (int)nt, ctx->m_out.as<Match>());
+  if (rc) return rc;
+  ctx->n_match = nq;
+  ctx->have_match = true;
+  if (n_out) *n_out = nq;
+  if (!out) return SIFT_OK;
+  if (cap < nq) return set_err(ctx, SIFT_E_CAPACITY, "match buffer too small");
+  if (nq) HIPCHK(d2h_staged(ctx, out, ctx->m_out.p, nq * sizeof(Match)));
+  return SIFT_OK;
+}
+
+int sift_device_matches(sift_ctx* ctx, const struct sift_match** d_match, size_t* n) {
+  if (!ctx || !d_match || !n) return SIFT_E_ARG;
+  if (!ctx->have_match) return set_err(ctx, SIFT_E_STATE, "no match: run sift_match or sift_match_features first");
+  *d_match = ctx->m_out.as<const struct sift_match>();
+  *n = ctx->n_match;
+  return SIFT_OK;
+}
+
+static int select_check(sift_ctx* ctx, const void* fwd, size_t n_query, size_t n_train, double ratio) {
+  if (!match_count_ok(n_query) || !match_count_ok(n_train)) return set_err(ctx, SIFT_E_ARG, "too many records");
+  if (n_query && !fwd) return set_err(ctx, SIFT_E_ARG, "null match records");
+  if (!(ratio <= 0.0) && !(std::isfinite(ratio) && ratio < 1.0))  // a NaN fails both
+    return set_err(ctx, SIFT_E_ARG, "ratio must be below 1, or <= 0 for no ratio test");
+  return SIFT_OK;
+}
+
+// Flags, their scan and the pair count of validated device records (nq > 0); starts the selection's timing.
+static int select_count(sift_ctx* ctx, const Match* fwd, int nq, const Match* rev, int nt, double ratio,
+                        unsigned* total) {
+  if (int rc = match_events(ctx)) return rc;
+  HIPCHK(ctx->m_flag.ensure((size_t)(nq + 1) * sizeof(unsigned)));
+  HIPCHK(ctx->m_off.ensure((size_t)(nq + 1) * sizeof(unsigned)));
+  unsigned* h_n = (unsigned*)ctx->hfeat.p + kFeatPairs;
+  HIPCHK(hipEventRecord(ctx->ev_m[2], ctx->stream));
+  HIPCHK(launch_match_flag(fwd, nq, rev, nt, ratio > 0.0 ? ratio * ratio : 0.0, ctx->m_flag.as<unsigned>(),
+                           ctx->stream));
+  HIPCHK(exclusive_sum(ctx, ctx->m_flag.as<unsigned>(), ctx->m_off.as<unsigned>(), nq + 1));
+  HIPCHK(hipMemcpyAsync(h_n, ctx->m_off.as<unsigned>() + nq, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *total = *h_n;
+  return SIFT_OK;
+}
+
+// Ends the selection's timing: after the ordered emission of `total` pairs, or
+// (d_pairs == nullptr: a count alone, or too small a buffer) after the count.
+static int select_emit(sift_ctx* ctx, const Match* fwd, int nq, unsigned total, MatchPair* d_pairs) {
+  if (d_pairs)
+    HIPCHK(launch_match_emit(fwd, ctx->m_flag.as<unsigned>(), ctx->m_off.as<unsigned>(), nq, total, d_pairs,
+                             ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev_m[3], ctx->stream));
+  HIPCHK(hipEventSynchronize(ctx->ev_m[3]));
+  float t = 0;
+  if (hipEventElapsedTime(&t, ctx->ev_m[2], ctx->ev_m[3]) == hipSuccess) ctx->select_ms = t;
+  return SIFT_OK;
+}
+
+int sift_match_select(sift_ctx* ctx, const struct sift_match* d_fwd, size_t n_query, const struct sift_match* d_rev, size_t n_train,
+                      double ratio, sift_match_pair* d_pairs, size_t cap, size_t* n_out) {
+  if (!ctx) return SIFT_E_ARG;
+  if (int rc = select_check(ctx, d_fwd, n_query, n_train, ratio)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->select_ms = 0;
+  unsigned total = 0;
+  if (n_query)
+    if (int rc = select_count(ctx, reinterpret_cast<const Match*>(d_fwd), (int)n_query,
+                              reinterpret_cast<const Match*>(d_rev), (int)n_train, ratio, &total))
+      return rc;
+  if (n_out) *n_out = total;
+  if (!n_query) return SIFT_OK;
+  if (!d_pairs || cap < total) {
+    if (int rc = select_emit(ctx, nullptr, (int)n_query, total, nullptr)) return rc;
+    return d_pairs ? set_err(ctx, SIFT_E_CAPACITY, "pair buffer too small") : SIFT_OK;
+  }
+  return select_emit(ctx, reinterpret_cast<const Match*>(d_fwd), (int)n_query, total,
+                     reinterpret_cast<MatchPair*>(d_pairs));
+}
+
+int sift_match_select_host(sift_ctx* ctx, const struct sift_match* fwd, size_t n_query, const struct sift_match* rev, size_t n_train,
+                           double ratio, sift_match_pair* pairs, size_t cap, size_t* n_out) {
+  if (!ctx) return SIFT_E_ARG;
+  if (int rc = select_check(ctx, fwd, n_query, n_train, ratio)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  ctx->select_ms = 0;
+  unsigned total = 0;
+  if (n_query) {
+    if (int rc = match_upload(ctx, ctx->m_fwd, fwd, n_query * sizeof(Match))) return rc;
+    if (int rc = match_upload(ctx, ctx->m_rev, rev, n_train * sizeof(Match))) return rc;
+    if (int rc = select_count(ctx, ctx->m_fwd.as<Match>(), (int)n_query,
+                              rev && n_train ? ctx->m_rev.as<Match>() : nullptr, (int)n_train, ratio, &total))
+      return rc;
+  }
+  if (n_out) *n_out = total;
+  if (!n_query) return SIFT_OK;
+  if (!pairs || cap < total) {
+    if (int rc = select_emit(ctx, nullptr, (int)n_query, total, nullptr)) return rc;
+    return pairs ? set_err(ctx, SIFT_E_CAPACITY, "pair buffer too small") : SIFT_OK;
+  }
+  HIPCHK(ctx->m_pairs.ensure(std::max<size_t>(total, 1) * sizeof(MatchPair)));
+  if (int rc = select_emit(ctx, ctx->m_fwd.as<Match>(), (int)n_query, total, ctx->m_pairs.as<MatchPair>())) return rc;
+  if (total) HIPCHK(d2h_staged(ctx, pairs, ctx->m_pairs.p, (size_t)total * sizeof(MatchPair)));
+  return SIFT_OK;
+}
+
+int sift_last_match_timings(sift_ctx* ctx, double* match_ms, double* select_ms) {
+  if (!ctx) return SIFT_E_ARG;
+  if (match_ms) *match_ms = ctx->match_ms;
+  if (select_ms) *select_ms = ctx->select_ms;
   return SIFT_OK;
 }
 

@@ -327,6 +327,55 @@ hipError_t launch_describe(const Pyramid& P, const float* gauss, int planes_firs
                            const Orientation* ori, int n, unsigned char* desc, unsigned char* described,
                            unsigned* n_described, hipStream_t st);
 
+// Descriptor matching (sift_match.hip).  Device twins of sift_match and of the
+// selected pair record (include/sift_hip.h), same 16-byte layouts.
+struct Match {
+  int32_t best, second, d2_best, d2_second;
+};
+struct MatchPair {
+  int32_t query, train, d2, d2_second;
+};
+constexpr int kMatchNQ = 4;                          // query fragments of 32 a wave keeps in registers
+constexpr int kMatchWaves = 4;                       // waves per block
+constexpr int kMatchQB = 32 * kMatchNQ * kMatchWaves;  // queries per block
+constexpr int kMatchChunk = 256;                     // train rows per key fold: the key's low byte is the row
+constexpr int kMatchBlocks = 1024;                   // blocks worth launching: four per CU
+// The train split, a function of the two counts alone: as many splits of whole
+// chunks as bring the grid to kMatchBlocks blocks, when the queries alone do not.
+struct MatchSplit {
+  int query_blocks, chunks, chunks_per_split, splits;
+};
+inline MatchSplit match_split(int n_query, int n_train) {
+  MatchSplit s{};
+  s.query_blocks = (int)(((long long)n_query + kMatchQB - 1) / kMatchQB);
+  s.chunks = (int)(((long long)n_train + kMatchChunk - 1) / kMatchChunk);
+  if (s.query_blocks < 1 || s.chunks < 1) return s;
+  const int want = std::min(s.chunks, (kMatchBlocks + s.query_blocks - 1) / s.query_blocks);
+  s.chunks_per_split = (s.chunks + want - 1) / want;
+  s.splits = (s.chunks + s.chunks_per_split - 1) / s.chunks_per_split;
+  return s;
+}
+inline long long match_query_rows(int n) { return ((long long)n + kMatchQB - 1) / kMatchQB * kMatchQB; }
+inline long long match_train_rows(int n) { return ((long long)n + kMatchChunk - 1) / kMatchChunk * kMatchChunk; }
+// dst = the n_pad-row packed copy of src's n rows of 128 bytes, each byte ^
+// 0x80, masked (mask[r] == 0; mask may be nullptr) and padding rows zero;
+// norm[r] = the shifted row's squared norm, -1 for those rows (train == 0), or
+// its key base (norm << 8) | (r & 255), INT32_MAX for those rows (train != 0).
+hipError_t launch_match_prep(const unsigned char* src, const unsigned char* mask, int n, long long n_pad, int train,
+                             unsigned char* dst, int* norm, hipStream_t st);
+// part[s n_query + q] = the top-2 of query q over the train rows of split s
+// (match_split(n_query, n_train).splits of them); qs / ts, qn / kb from launch_match_prep.
+hipError_t launch_match(const unsigned char* qs, const int* qn, int n_query, const unsigned char* ts, const int* kb,
+                        int n_train, Match* part, hipStream_t st);
+// out[q] = the top-2 over the splits' records; splits == 0 writes missing neighbours.
+hipError_t launch_match_merge(const Match* part, int splits, int n_query, Match* out, hipStream_t st);
+// flag[q] = fwd[q] is accepted (q < n_query), flag[n_query] = 0; r2 = ratio^2 or <= 0; rev may be nullptr.
+hipError_t launch_match_flag(const Match* fwd, int n_query, const Match* rev, int n_train, double r2, unsigned* flag,
+                             hipStream_t st);
+// off = the exclusive scan of flag: the accepted pairs in ascending query index (cap slots).
+hipError_t launch_match_emit(const Match* fwd, const unsigned* flag, const unsigned* off, int n_query, unsigned cap,
+                             MatchPair* out, hipStream_t st);
+
 // Image products either side of the path (sift_image.hip).
 // gray/alpha rows are dense (w floats); alpha may be nullptr.
 hipError_t launch_rgba_to_gray(const unsigned char* rgba, size_t stride_bytes, int w, int h, float* gray,

@@ -61,6 +61,8 @@ ABI_SYMBOLS = (
     "sift_detect_batch_device", "sift_detect_batch_device_async", "sift_detect_batch",
     "sift_orient", "sift_describe", "sift_device_features", "sift_last_feature_timings",
     "sift_set_keypoints", "sift_set_orientations",
+    "sift_match_device", "sift_match", "sift_match_features", "sift_device_matches",
+    "sift_match_select", "sift_match_select_host", "sift_last_match_timings",
 )
 
 
@@ -110,6 +112,9 @@ KEYPOINT_DTYPE = np.dtype([("octave", "<i4"), ("scale_level", "<i4"), ("local_x"
 
 ORIENTATION_DTYPE = np.dtype([("keypoint", "<i4"), ("bin", "<i4"), ("theta", "<f8")])
 DESC_BYTES = 128
+MATCH_DTYPE = np.dtype([("best", "<i4"), ("second", "<i4"), ("d2_best", "<i4"), ("d2_second", "<i4")])
+PAIR_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("d2", "<i4"), ("d2_second", "<i4")])
+MATCH_NONE_D2 = 2**31 - 1
 
 _lib = None
 
@@ -206,6 +211,13 @@ def lib():
         "sift_last_feature_timings": (ctypes.c_int, [vp, dp, dp]),
         "sift_set_keypoints": (ctypes.c_int, [vp, vp, sz]),
         "sift_set_orientations": (ctypes.c_int, [vp, vp, sz]),
+        "sift_match_device": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, vp]),
+        "sift_match": (ctypes.c_int, [vp, vp, vp, sz, vp, vp, sz, vp]),
+        "sift_match_features": (ctypes.c_int, [vp, vp, vp, sz, szp]),
+        "sift_device_matches": (ctypes.c_int, [vp, ctypes.POINTER(vp), szp]),
+        "sift_match_select": (ctypes.c_int, [vp, vp, sz, vp, sz, ctypes.c_double, vp, sz, szp]),
+        "sift_match_select_host": (ctypes.c_int, [vp, vp, sz, vp, sz, ctypes.c_double, vp, sz, szp]),
+        "sift_last_match_timings": (ctypes.c_int, [vp, dp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -733,6 +745,75 @@ class Context:
         self._check(self._L.sift_last_feature_timings(self._h, ctypes.byref(a), ctypes.byref(b)),
                     "sift_last_feature_timings")
         return dict(orient_ms=a.value, describe_ms=b.value)
+
+    # -- descriptor matching -------------------------------------------------
+    @staticmethod
+    def _rows(a):
+        a = np.ascontiguousarray(a, dtype=np.uint8)
+        if a.ndim != 2 or a.shape[1] != DESC_BYTES:
+            raise ValueError("descriptors must be uint8 [n, %d]" % DESC_BYTES)
+        return a
+
+    @staticmethod
+    def _mask(m, n):
+        if m is None:
+            return None
+        m = np.ascontiguousarray(np.asarray(m) != 0, dtype=np.uint8)
+        if m.shape != (n,):
+            raise ValueError("mask must have one entry per row")
+        return m
+
+    @staticmethod
+    def _ptr(a):
+        return a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None
+
+    def match(self, query, train, query_mask=None, train_mask=None):
+        """The two nearest train rows of every query row by squared L2 distance
+        (sift_match): MATCH_DTYPE [n_query].  Masks: nonzero = the row takes part."""
+        q, t = self._rows(query), self._rows(train)
+        qm, tm = self._mask(query_mask, q.shape[0]), self._mask(train_mask, t.shape[0])
+        out = np.zeros(q.shape[0], dtype=MATCH_DTYPE)
+        self._check(self._L.sift_match(self._h, self._ptr(q), self._ptr(qm), q.shape[0], self._ptr(t), self._ptr(tm),
+                                       t.shape[0], self._ptr(out)), "sift_match")
+        return out
+
+    def match_features(self, train_ctx):
+        """This context's last describe() against train_ctx's, on the device
+        (sift_match_features): MATCH_DTYPE [records of this context]."""
+        n = ctypes.c_size_t()
+        self._L.sift_device_features(self._h, None, None, None, ctypes.byref(n))  # the record count; 0 without features
+        out = np.zeros(max(n.value, 1), dtype=MATCH_DTYPE)
+        self._check(self._L.sift_match_features(self._h, train_ctx._h, out.ctypes.data_as(ctypes.c_void_p),
+                                                out.shape[0], ctypes.byref(n)), "sift_match_features")
+        return out[:n.value]
+
+    def device_matches(self):
+        """Device pointer and count of the last match()'s / match_features()'s records."""
+        p, n = ctypes.c_void_p(), ctypes.c_size_t()
+        self._check(self._L.sift_device_matches(self._h, ctypes.byref(p), ctypes.byref(n)), "sift_device_matches")
+        return p.value or 0, n.value
+
+    def select_matches(self, fwd, rev=None, ratio=0.8):
+        """The accepted pairs of fwd (query -> train records of match()), in
+        ascending query index: PAIR_DTYPE.  ratio <= 0: no ratio test; rev (the
+        train -> query records of the swapped match): a mutual check
+        (sift_match_select_host)."""
+        f = np.ascontiguousarray(fwd, dtype=MATCH_DTYPE)
+        r = None if rev is None else np.ascontiguousarray(rev, dtype=MATCH_DTYPE)
+        out = np.zeros(max(f.shape[0], 1), dtype=PAIR_DTYPE)
+        n = ctypes.c_size_t()
+        self._check(self._L.sift_match_select_host(self._h, self._ptr(f), f.shape[0], self._ptr(r),
+                                                   0 if r is None else r.shape[0], float(ratio),
+                                                   out.ctypes.data_as(ctypes.c_void_p), out.shape[0],
+                                                   ctypes.byref(n)), "sift_match_select_host")
+        return out[:n.value]
+
+    def match_timings(self):
+        """Device ms of the last match and the last selection."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        self._check(self._L.sift_last_match_timings(self._h, ctypes.byref(a), ctypes.byref(b)),
+                    "sift_last_match_timings")
+        return dict(match_ms=a.value, select_ms=b.value)
 
     def stream(self):
         return self._L.sift_stream(self._h)
