@@ -587,6 +587,121 @@ int sift_match_select_host(struct sift_ctx *ctx, const struct sift_match *fwd, s
  * were written), milliseconds. */
 int sift_last_match_timings(struct sift_ctx *ctx, double *match_ms, double *select_ms);
 
+/* ---- RANSAC homography verification of match pairs ------------------------
+ *
+ * A homography fitted to the putative pairs of the selection above, on the
+ * device and bit-identical from run to run.  The definition uses only + - * /
+ * and comparisons in fp64 with no contraction (no fused multiply-add) and no
+ * sqrt, so that a plain restatement reproduces it bit for bit.  Like the stages
+ * above, these entry points are detected by symbol; SIFT_ABI_VERSION stays 9.
+ *
+ * Model: H is row-major h[0..8] and maps query to train: (u, v, w) = H (x, y, 1),
+ * the image point is (u/w, v/w).
+ *
+ * Hypothesis k (0 <= k < K) for seed s (uint64) over n >= 4 pairs:
+ *  1. Four distinct indices.  For draw i = 0..3:
+ *       z = mix(s + (4 k + i + 1) * 0x9E3779B97F4A7C15)            (mod 2^64),
+ *       mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) *
+ *               0x94D049BB133111EB; z ^ (z >> 31)    (splitmix64's output mixer),
+ *       r = ((z >> 32) * (n - i)) >> 32,
+ *       then for every earlier chosen index c in ascending order: if (r >= c) r++.
+ *     No rejection loop; the sample keeps draw order.
+ *  2. The 8 x 9 system in the unknowns h[0..7], h[8] = 1.  Sample j with
+ *     (x, y) -> (X, Y) gives
+ *       row 2j   = [x, y, 1, 0, 0, 0, -X*x, -X*y | X],
+ *       row 2j+1 = [0, 0, 0, x, y, 1, -Y*x, -Y*y | Y].
+ *  3. Gaussian elimination with partial pivoting.  For column c = 0..7 the pivot
+ *     row is the row r >= c of largest |A[r][c]| (p = c; a later row replaces it
+ *     only when strictly larger, so a NaN never does), lowest r among equals.  A
+ *     pivot that is zero or not finite makes the hypothesis invalid.  Swap the
+ *     rows; for each r > c: f = A[r][c] / A[c][c], and for j = c+1..8:
+ *     A[r][j] = A[r][j] - f * A[c][j].  Back substitution for c = 7..0:
+ *     t = A[c][8]; for j = c+1..7 ascending: t = t - A[c][j] * h[j]; h[c] = t /
+ *     A[c][c].  A non-finite h makes the hypothesis invalid.
+ *     An invalid hypothesis has H = nine zeros and count -1.
+ *  4. No coordinate normalisation.
+ *
+ * Inlier rule for a pair (x, y) -> (X, Y), a matrix h and t2 = thresh * thresh
+ * (formed once on the host):
+ *       u = (h0*x + h1*y) + h2, v = (h3*x + h4*y) + h5, w = (h6*x + h7*y) + h8,
+ *       du = u - X*w, dv = v - Y*w,
+ *       inlier iff w > 0 && (du*du + dv*dv) < t2 * (w*w).
+ * No division; a NaN in a point or a coefficient compares false, so that pair
+ * is never an inlier.
+ *
+ * Result: the count of a valid hypothesis is its number of inliers over all n
+ * pairs; the best hypothesis has the largest count, lowest k among equals; the
+ * inlier list holds the pair indices of the best hypothesis in ascending order.
+ * If n < 4, K == 0 or every hypothesis is invalid the result is hypothesis = -1,
+ * inliers = 0, nine zeros and an empty list, and the call is valid (with n < 4
+ * or K == 0 no hypothesis is formed: sift_copy_homography_hypotheses gives 0).
+ *
+ * Limits: K <= SIFT_RANSAC_MAX_HYPOTHESES, n < 2^31 - 1, thresh finite and > 0,
+ * pointers non-NULL where a count is non-zero: else SIFT_E_ARG, nothing written.
+ *
+ * Not here: a least-squares refit over the inliers (it needs an ordered fp64
+ * reduction of its own and builds on the inlier list returned), symmetric
+ * transfer error, adaptive termination, fundamental or essential matrices. */
+#define SIFT_RANSAC_MAX_HYPOTHESES 65536
+
+/* A point of the query image and its putative partner in the train image, in
+ * absolute input-pixel units (abs_x, abs_y of sift_keypoint). */
+typedef struct {
+  double qx, qy, tx, ty;
+} sift_point_pair; /* 32 bytes */
+
+typedef struct {
+  double h[9];
+  int32_t hypothesis; /* index k of the best hypothesis, -1: none */
+  int32_t inliers;    /* its count */
+} sift_homography; /* 80 bytes */
+
+/* d_points[i] = the keypoint positions behind d_pairs[i] (n records of
+ * sift_match_select): `query` / `train` index the orientation records of ctx /
+ * train_ctx (the rows sift_match_features matched), whose `keypoint` indexes the
+ * keypoint list.  An index outside its list gives four NaNs (such a pair is
+ * never an inlier).  Device memory of ctx's device; complete on return.
+ * SIFT_E_STATE without a sift_orient on either side. */
+int sift_pair_points_device(struct sift_ctx *ctx, struct sift_ctx *train_ctx, const sift_match_pair *d_pairs, size_t n,
+                            sift_point_pair *d_points);
+
+/* RANSAC over n device point pairs: K hypotheses for `seed`, scored at `thresh`
+ * (input pixels).  *model (host memory) receives the best hypothesis, *n_inliers
+ * its count; d_inliers (device memory, cap indices) the inlier list, or NULL to
+ * only count.  SIFT_E_CAPACITY when cap < *n_inliers: *model and *n_inliers are
+ * set, the list is not written.  Complete on return. */
+int sift_homography_ransac_device(struct sift_ctx *ctx, const sift_point_pair *d_points, size_t n, size_t K,
+                                  uint64_t seed, double thresh, sift_homography *model, int32_t *d_inliers, size_t cap,
+                                  size_t *n_inliers);
+/* The same with host points and a host inlier list, through the context's own device buffers. */
+int sift_homography_ransac(struct sift_ctx *ctx, const sift_point_pair *points, size_t n, size_t K, uint64_t seed,
+                           double thresh, sift_homography *model, int32_t *inliers, size_t cap, size_t *n_inliers);
+
+/* counts[k] = the inliers among the n pairs of the caller's matrix H[9 k ..
+ * 9 k + 8] (k < K, h[8] as given), by the inlier rule alone.  Host arrays;
+ * _device: device arrays, complete on return. */
+int sift_homography_score(struct sift_ctx *ctx, const sift_point_pair *points, size_t n, const double *H, size_t K,
+                          double thresh, int32_t *counts);
+int sift_homography_score_device(struct sift_ctx *ctx, const sift_point_pair *d_points, size_t n, const double *d_H,
+                                 size_t K, double thresh, int32_t *d_counts);
+
+/* Every hypothesis (9 doubles each) and count (-1: invalid) of the last RANSAC
+ * on ctx, into host memory; cap in hypotheses; either array may be NULL.
+ * SIFT_E_STATE without one; SIFT_E_CAPACITY: *n_out = required count. */
+int sift_copy_homography_hypotheses(struct sift_ctx *ctx, double *H, int32_t *counts, size_t cap, size_t *n_out);
+
+/* Host pairs in (the output of sift_match_select_host between ctx and
+ * train_ctx), point gather plus RANSAC on the device, host results out:
+ * sift_pair_points_device followed by sift_homography_ransac. */
+int sift_verify_features(struct sift_ctx *ctx, struct sift_ctx *train_ctx, const sift_match_pair *pairs, size_t n,
+                         size_t K, uint64_t seed, double thresh, sift_homography *model, int32_t *inliers, size_t cap,
+                         size_t *n_inliers);
+
+/* Device time of the last RANSAC's stages, milliseconds: the hypotheses, their
+ * scoring (sift_homography_score* sets this one alone), and the selection (best
+ * hypothesis, flags, scan, count read-back, and the emission when written). */
+int sift_last_verify_timings(struct sift_ctx *ctx, double *hypotheses_ms, double *score_ms, double *select_ms);
+
 /* Wait for all work queued on ctx's stream. */
 int sift_synchronize(struct sift_ctx *ctx);
 

@@ -238,6 +238,16 @@ struct sift_ctx {
   bool have_match = false;
   hipEvent_t ev_m[4]{};                        // around the match [0, 1] and the selection [2, 3]
   double match_ms = 0, select_ms = 0;
+  // homography verification (sift_verify.hip)
+  DBuf v_H, v_valid, v_cnt, v_model;           // the last RANSAC's hypotheses, valid flags, counts; its model record
+  DBuf v_flag, v_off;                          // inlier flags of the best model, their scan
+  DBuf v_in_pts, v_in_H, v_in_cnt, v_pairs;    // host-form inputs and counts (sift_homography_score, sift_verify_features)
+  DBuf v_pts, v_inl;                           // gathered points (sift_verify_features); host-form inlier list
+  HBuf hver;                                   // pinned: the model record, then the inlier count
+  size_t n_hyp = 0;                            // hypotheses in v_H / v_cnt
+  bool have_ransac = false;
+  hipEvent_t ev_v[6]{};                        // around the hypotheses [0, 1], the scoring [2, 3], the selection [4, 5]
+  double v_hyp_ms = 0, v_score_ms = 0, v_select_ms = 0;
   DBuf counters, temp;
   DBuf rgba, alpha, display, mm_parts;         // image products (sift_image.hip)
   unsigned* h_counters = nullptr;              // pinned mirror of counters (+ per-block keypoint counts at kBlk)
@@ -263,6 +273,8 @@ struct sift_ctx {
     for (auto& e : ev_f)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_m)
+      if (e) (void)hipEventDestroy(e);
+    for (auto& e : ev_v)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : ev_pl)
       if (e) (void)hipEventDestroy(e);
@@ -2410,6 +2422,235 @@ int sift_last_match_timings(sift_ctx* ctx, double* match_ms, double* select_ms) 
   if (!ctx) return SIFT_E_ARG;
   if (match_ms) *match_ms = ctx->match_ms;
   if (select_ms) *select_ms = ctx->select_ms;
+  return SIFT_OK;
+}
+
+// ---- Homography verification (sift_verify.hip) ------------------------------
+static_assert(sizeof(sift_point_pair) == 32 && sizeof(PointPair) == 32 && sizeof(sift_homography) == 80 &&
+                  sizeof(Homography) == 80 && SIFT_RANSAC_MAX_HYPOTHESES == kMaxHypotheses,
+              "verification records and limits of include/sift_hip.h");
+
+static int verify_events(sift_ctx* ctx) {
+  for (auto& e : ctx->ev_v)
+    if (!e) HIPCHK(hipEventCreate(&e));
+  HIPCHK(ctx->hver.ensure(sizeof(Homography) + sizeof(unsigned)));
+  return SIFT_OK;
+}
+
+static int verify_check(sift_ctx* ctx, const void* points, size_t n, size_t K, double thresh) {
+  if (!match_count_ok(n)) return set_err(ctx, SIFT_E_ARG, "too many pairs");
+  if (K > (size_t)kMaxHypotheses) return set_err(ctx, SIFT_E_ARG, "more than SIFT_RANSAC_MAX_HYPOTHESES hypotheses");
+  if (!(std::isfinite(thresh) && thresh > 0.0)) return set_err(ctx, SIFT_E_ARG, "thresh must be finite and > 0");
+  if (n && !points) return set_err(ctx, SIFT_E_ARG, "null pairs");
+  return SIFT_OK;
+}
+
+static double event_ms(hipEvent_t a, hipEvent_t b) {
+  float t = 0;
+  return hipEventElapsedTime(&t, a, b) == hipSuccess ? t : 0.0;
+}
+
+// counts[k] of validated device arrays (K > 0), between the scoring's two events; not waited for.
+static int score_enqueue(sift_ctx* ctx, const PointPair* pts, int n, const double* H, int K, double t2, int* counts) {
+  HIPCHK(hipEventRecord(ctx->ev_v[2], ctx->stream));
+  HIPCHK(hipMemsetAsync(counts, 0, (size_t)K * sizeof(int), ctx->stream));
+  HIPCHK(launch_homography_score(pts, n, H, K, t2, counts, ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev_v[3], ctx->stream));
+  return SIFT_OK;
+}
+
+static int score_run(sift_ctx* ctx, const PointPair* pts, size_t n, const double* H, size_t K, double thresh,
+                     int* counts) {
+  if (int rc = verify_events(ctx)) return rc;
+  ctx->v_score_ms = 0;
+  if (!K) return SIFT_OK;
+  if (int rc = score_enqueue(ctx, pts, (int)n, H, (int)K, thresh * thresh, counts)) return rc;
+  HIPCHK(hipEventSynchronize(ctx->ev_v[3]));
+  ctx->v_score_ms = event_ms(ctx->ev_v[2], ctx->ev_v[3]);
+  return SIFT_OK;
+}
+
+int sift_homography_score_device(sift_ctx* ctx, const sift_point_pair* d_points, size_t n, const double* d_H, size_t K,
+                                 double thresh, int32_t* d_counts) {
+  if (!ctx) return SIFT_E_ARG;
+  if (int rc = verify_check(ctx, d_points, n, K, thresh)) return rc;
+  if (K && (!d_H || !d_counts)) return set_err(ctx, SIFT_E_ARG, "null matrices or counts");
+  HIPCHK(hipSetDevice(ctx->device));
+  return score_run(ctx, reinterpret_cast<const PointPair*>(d_points), n, d_H, K, thresh, d_counts);
+}
+
+int sift_homography_score(sift_ctx* ctx, const sift_point_pair* points, size_t n, const double* H, size_t K,
+                          double thresh, int32_t* counts) {
+  if (!ctx) return SIFT_E_ARG;
+  if (int rc = verify_check(ctx, points, n, K, thresh)) return rc;
+  if (K && (!H || !counts)) return set_err(ctx, SIFT_E_ARG, "null matrices or counts");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (!K) return score_run(ctx, nullptr, n, nullptr, 0, thresh, nullptr);
+  if (int rc = match_upload(ctx, ctx->v_in_pts, points, n * sizeof(PointPair))) return rc;
+  if (int rc = match_upload(ctx, ctx->v_in_H, H, K * 9 * sizeof(double))) return rc;
+  HIPCHK(ctx->v_in_cnt.ensure(K * sizeof(int)));
+  if (int rc = score_run(ctx, ctx->v_in_pts.as<PointPair>(), n, ctx->v_in_H.as<double>(), K, thresh,
+                         ctx->v_in_cnt.as<int>()))
+    return rc;
+  HIPCHK(d2h_staged(ctx, counts, ctx->v_in_cnt.p, K * sizeof(int)));
+  return SIFT_OK;
+}
+
+// RANSAC over validated device points: the model and the count always, the
+// list into d_inliers when it is given and cap holds it.
+static int ransac_run(sift_ctx* ctx, const PointPair* pts, size_t n, size_t K, uint64_t seed, double thresh,
+                      sift_homography* model, int32_t* d_inliers, size_t cap, size_t* n_inliers) {
+  if (int rc = verify_events(ctx)) return rc;
+  ctx->v_hyp_ms = ctx->v_score_ms = ctx->v_select_ms = 0;
+  ctx->have_ransac = false;
+  ctx->n_hyp = 0;
+  if (n < 4 || K == 0) {  // no hypothesis is formed
+    std::memset(model, 0, sizeof *model);
+    model->hypothesis = -1;
+    if (n_inliers) *n_inliers = 0;
+    ctx->have_ransac = true;
+    return SIFT_OK;
+  }
+  const int ni = (int)n, Ki = (int)K;
+  const double t2 = thresh * thresh;
+  HIPCHK(ctx->v_H.ensure(K * 9 * sizeof(double)));
+  HIPCHK(ctx->v_valid.ensure(K * sizeof(int)));
+  HIPCHK(ctx->v_cnt.ensure(K * sizeof(int)));
+  HIPCHK(ctx->v_model.ensure(sizeof(Homography)));
+  HIPCHK(ctx->v_flag.ensure((n + 1) * sizeof(unsigned)));
+  HIPCHK(ctx->v_off.ensure((n + 1) * sizeof(unsigned)));
+  Homography* h_model = (Homography*)ctx->hver.p;
+  unsigned* h_n = (unsigned*)(h_model + 1);
+  HIPCHK(hipEventRecord(ctx->ev_v[0], ctx->stream));
+  HIPCHK(launch_homography_hypotheses(pts, ni, Ki, seed, ctx->v_H.as<double>(), ctx->v_valid.as<int>(), ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev_v[1], ctx->stream));
+  if (int rc = score_enqueue(ctx, pts, ni, ctx->v_H.as<double>(), Ki, t2, ctx->v_cnt.as<int>())) return rc;
+  HIPCHK(hipEventRecord(ctx->ev_v[4], ctx->stream));
+  HIPCHK(launch_homography_best(ctx->v_H.as<double>(), ctx->v_valid.as<int>(), ctx->v_cnt.as<int>(), Ki,
+                                ctx->v_model.as<Homography>(), ctx->stream));
+  HIPCHK(launch_inlier_flag(pts, ni, ctx->v_model.as<Homography>(), t2, ctx->v_flag.as<unsigned>(), ctx->stream));
+  HIPCHK(exclusive_sum(ctx, ctx->v_flag.as<unsigned>(), ctx->v_off.as<unsigned>(), ni + 1));
+  HIPCHK(hipMemcpyAsync(h_model, ctx->v_model.p, sizeof(Homography), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipMemcpyAsync(h_n, ctx->v_off.as<unsigned>() + ni, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  const unsigned total = *h_n;
+  std::memcpy(model, h_model, sizeof *model);
+  if (n_inliers) *n_inliers = total;
+  const bool fits = cap >= total;
+  if (d_inliers && fits)
+    HIPCHK(launch_inlier_emit(ctx->v_flag.as<unsigned>(), ctx->v_off.as<unsigned>(), ni, total, d_inliers,
+                              ctx->stream));
+  HIPCHK(hipEventRecord(ctx->ev_v[5], ctx->stream));
+  HIPCHK(hipEventSynchronize(ctx->ev_v[5]));
+  ctx->v_hyp_ms = event_ms(ctx->ev_v[0], ctx->ev_v[1]);
+  ctx->v_score_ms = event_ms(ctx->ev_v[2], ctx->ev_v[3]);
+  ctx->v_select_ms = event_ms(ctx->ev_v[4], ctx->ev_v[5]);
+  ctx->n_hyp = K;
+  ctx->have_ransac = true;
+  if (d_inliers && !fits) return set_err(ctx, SIFT_E_CAPACITY, "inlier buffer too small");
+  return SIFT_OK;
+}
+
+int sift_homography_ransac_device(sift_ctx* ctx, const sift_point_pair* d_points, size_t n, size_t K, uint64_t seed,
+                                  double thresh, sift_homography* model, int32_t* d_inliers, size_t cap,
+                                  size_t* n_inliers) {
+  if (!ctx) return SIFT_E_ARG;
+  if (int rc = verify_check(ctx, d_points, n, K, thresh)) return rc;
+  if (!model) return set_err(ctx, SIFT_E_ARG, "null model");
+  HIPCHK(hipSetDevice(ctx->device));
+  return ransac_run(ctx, reinterpret_cast<const PointPair*>(d_points), n, K, seed, thresh, model, d_inliers, cap,
+                    n_inliers);
+}
+
+// ransac_run with the list through ctx->v_inl into host memory.
+static int ransac_to_host(sift_ctx* ctx, const PointPair* pts, size_t n, size_t K, uint64_t seed, double thresh,
+                          sift_homography* model, int32_t* inliers, size_t cap, size_t* n_inliers) {
+  if (inliers) HIPCHK(ctx->v_inl.ensure(std::max<size_t>(n, 1) * sizeof(int32_t)));
+  size_t total = 0;
+  if (int rc = ransac_run(ctx, pts, n, K, seed, thresh, model, inliers ? ctx->v_inl.as<int32_t>() : nullptr, cap,
+                          &total)) {
+    if (rc == SIFT_E_CAPACITY && n_inliers) *n_inliers = total;
+    return rc;
+  }
+  if (n_inliers) *n_inliers = total;
+  if (inliers && total) HIPCHK(d2h_staged(ctx, inliers, ctx->v_inl.p, total * sizeof(int32_t)));
+  return SIFT_OK;
+}
+
+int sift_homography_ransac(sift_ctx* ctx, const sift_point_pair* points, size_t n, size_t K, uint64_t seed,
+                           double thresh, sift_homography* model, int32_t* inliers, size_t cap, size_t* n_inliers) {
+  if (!ctx) return SIFT_E_ARG;
+  if (int rc = verify_check(ctx, points, n, K, thresh)) return rc;
+  if (!model) return set_err(ctx, SIFT_E_ARG, "null model");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = match_upload(ctx, ctx->v_in_pts, points, n * sizeof(PointPair))) return rc;
+  return ransac_to_host(ctx, ctx->v_in_pts.as<PointPair>(), n, K, seed, thresh, model, inliers, cap, n_inliers);
+}
+
+int sift_copy_homography_hypotheses(sift_ctx* ctx, double* H, int32_t* counts, size_t cap, size_t* n_out) {
+  if (!ctx) return SIFT_E_ARG;
+  if (!ctx->have_ransac) return set_err(ctx, SIFT_E_STATE, "no RANSAC: run sift_homography_ransac first");
+  const size_t K = ctx->n_hyp;
+  if (n_out) *n_out = K;
+  if ((!H && !counts) || !K) return SIFT_OK;
+  if (cap < K) return set_err(ctx, SIFT_E_CAPACITY, "hypothesis buffer too small");
+  HIPCHK(hipSetDevice(ctx->device));
+  if (H) HIPCHK(d2h_staged(ctx, H, ctx->v_H.p, K * 9 * sizeof(double)));
+  if (counts) HIPCHK(d2h_staged(ctx, counts, ctx->v_cnt.p, K * sizeof(int)));
+  return SIFT_OK;
+}
+
+// Both sides have the orientation records the pairs index, on one device.
+static int pair_points_check(sift_ctx* ctx, sift_ctx* train_ctx) {
+  for (sift_ctx* c : {ctx, train_ctx})
+    if (c->detect_pending || c->begin_pending || !c->have_kp || !c->have_ori)
+      return set_err(ctx, SIFT_E_STATE, "no orientations: run sift_orient on both contexts first");
+  if (ctx->device != train_ctx->device) return set_err(ctx, SIFT_E_ARG, "contexts on different devices");
+  return SIFT_OK;
+}
+
+static int pair_points_enqueue(sift_ctx* ctx, sift_ctx* train_ctx, const MatchPair* d_pairs, size_t n,
+                               PointPair* d_points) {
+  HIPCHK(launch_pair_points(d_pairs, (int)n, ctx->ori.as<Orientation>(), (int)ctx->n_ori, ctx->kp.as<Keypoint>(),
+                            (int)ctx->n_kp, train_ctx->ori.as<Orientation>(), (int)train_ctx->n_ori,
+                            train_ctx->kp.as<Keypoint>(), (int)train_ctx->n_kp, d_points, ctx->stream));
+  return SIFT_OK;
+}
+
+int sift_pair_points_device(sift_ctx* ctx, sift_ctx* train_ctx, const sift_match_pair* d_pairs, size_t n,
+                            sift_point_pair* d_points) {
+  if (!ctx || !train_ctx) return SIFT_E_ARG;
+  if (!match_count_ok(n)) return set_err(ctx, SIFT_E_ARG, "too many pairs");
+  if (n && (!d_pairs || !d_points)) return set_err(ctx, SIFT_E_ARG, "null pairs or points");
+  if (int rc = pair_points_check(ctx, train_ctx)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = pair_points_enqueue(ctx, train_ctx, reinterpret_cast<const MatchPair*>(d_pairs), n,
+                                   reinterpret_cast<PointPair*>(d_points)))
+    return rc;
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  return SIFT_OK;
+}
+
+int sift_verify_features(sift_ctx* ctx, sift_ctx* train_ctx, const sift_match_pair* pairs, size_t n, size_t K,
+                         uint64_t seed, double thresh, sift_homography* model, int32_t* inliers, size_t cap,
+                         size_t* n_inliers) {
+  if (!ctx || !train_ctx) return SIFT_E_ARG;
+  if (int rc = verify_check(ctx, pairs, n, K, thresh)) return rc;
+  if (!model) return set_err(ctx, SIFT_E_ARG, "null model");
+  if (int rc = pair_points_check(ctx, train_ctx)) return rc;
+  HIPCHK(hipSetDevice(ctx->device));
+  if (int rc = match_upload(ctx, ctx->v_pairs, pairs, n * sizeof(MatchPair))) return rc;
+  HIPCHK(ctx->v_pts.ensure(std::max<size_t>(n, 1) * sizeof(PointPair)));
+  if (int rc = pair_points_enqueue(ctx, train_ctx, ctx->v_pairs.as<MatchPair>(), n, ctx->v_pts.as<PointPair>()))
+    return rc;
+  return ransac_to_host(ctx, ctx->v_pts.as<PointPair>(), n, K, seed, thresh, model, inliers, cap, n_inliers);
+}
+
+int sift_last_verify_timings(sift_ctx* ctx, double* hypotheses_ms, double* score_ms, double* select_ms) {
+  if (!ctx) return SIFT_E_ARG;
+  if (hypotheses_ms) *hypotheses_ms = ctx->v_hyp_ms;
+  if (score_ms) *score_ms = ctx->v_score_ms;
+  if (select_ms) *select_ms = ctx->v_select_ms;
   return SIFT_OK;
 }
 

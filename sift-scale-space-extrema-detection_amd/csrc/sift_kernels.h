@@ -376,6 +376,55 @@ hipError_t launch_match_flag(const Match* fwd, int n_query, const Match* rev, in
 hipError_t launch_match_emit(const Match* fwd, const unsigned* flag, const unsigned* off, int n_query, unsigned cap,
                              MatchPair* out, hipStream_t st);
 
+// RANSAC homography verification of match pairs (sift_verify.hip).  Device
+// twins of sift_point_pair and sift_homography (include/sift_hip.h), same layouts.
+struct PointPair {
+  double qx, qy, tx, ty;
+};
+struct Homography {
+  double h[9];
+  int32_t hypothesis, inliers;
+};
+constexpr int kMaxHypotheses = 65536;
+constexpr int kScoreR = 4;                            // pairs a lane keeps in registers
+constexpr int kScoreWaves = 4;                        // waves per block
+constexpr int kScorePairs = 64 * kScoreWaves * kScoreR;  // pairs per block
+constexpr int kScoreTile = 64;                        // hypotheses a block walks
+// The inlier rule of include/sift_hip.h, the one statement of it: the score
+// kernel, the flag kernel and nothing else decide with it.  (x, y) -> (X, Y)
+// under row-major h; no division; a NaN anywhere compares false.
+__host__ __device__ inline bool homography_inlier(double h0, double h1, double h2, double h3, double h4, double h5,
+                                                  double h6, double h7, double h8, double x, double y, double X,
+                                                  double Y, double t2) {
+#pragma clang fp contract(off)
+  const double u = (h0 * x + h1 * y) + h2;
+  const double v = (h3 * x + h4 * y) + h5;
+  const double w = (h6 * x + h7 * y) + h8;
+  const double du = u - X * w, dv = v - Y * w;
+  const bool front = w > 0.0, near = (du * du + dv * dv) < t2 * (w * w);
+  return front & near;  // both evaluated: no branch around the second in the score loop
+}
+// points[i] = (abs_x, abs_y) of the query and of the train keypoint behind pair
+// i's orientation records; four NaNs when an index is outside its list.
+hipError_t launch_pair_points(const MatchPair* pairs, int n, const Orientation* q_ori, int nq_ori, const Keypoint* q_kp,
+                              int nq_kp, const Orientation* t_ori, int nt_ori, const Keypoint* t_kp, int nt_kp,
+                              PointPair* points, hipStream_t st);
+// H[9 k ..], valid[k] of hypothesis k < K for this seed over n >= 4 pairs.
+hipError_t launch_homography_hypotheses(const PointPair* points, int n, int K, unsigned long long seed, double* H,
+                                        int* valid, hipStream_t st);
+// counts[k] += the inliers of H[9 k ..] among the n pairs (counts zeroed by the caller).
+hipError_t launch_homography_score(const PointPair* points, int n, const double* H, int K, double t2, int* counts,
+                                   hipStream_t st);
+// counts[k] = -1 where !valid[k]; *model = the arg-max of (count, -k), or (-1, 0, zeros).
+hipError_t launch_homography_best(const double* H, const int* valid, int* counts, int K, Homography* model,
+                                  hipStream_t st);
+// flag[i] = pair i is an inlier of *model (i < n), flag[n] = 0.
+hipError_t launch_inlier_flag(const PointPair* points, int n, const Homography* model, double t2, unsigned* flag,
+                              hipStream_t st);
+// off = the exclusive scan of flag: the inlier indices in ascending order (cap slots).
+hipError_t launch_inlier_emit(const unsigned* flag, const unsigned* off, int n, unsigned cap, int32_t* out,
+                              hipStream_t st);
+
 // Image products either side of the path (sift_image.hip).
 // gray/alpha rows are dense (w floats); alpha may be nullptr.
 hipError_t launch_rgba_to_gray(const unsigned char* rgba, size_t stride_bytes, int w, int h, float* gray,

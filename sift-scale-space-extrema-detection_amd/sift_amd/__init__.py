@@ -63,6 +63,9 @@ ABI_SYMBOLS = (
     "sift_set_keypoints", "sift_set_orientations",
     "sift_match_device", "sift_match", "sift_match_features", "sift_device_matches",
     "sift_match_select", "sift_match_select_host", "sift_last_match_timings",
+    "sift_pair_points_device", "sift_homography_ransac_device", "sift_homography_ransac",
+    "sift_homography_score", "sift_homography_score_device", "sift_copy_homography_hypotheses",
+    "sift_verify_features", "sift_last_verify_timings",
 )
 
 
@@ -115,6 +118,12 @@ DESC_BYTES = 128
 MATCH_DTYPE = np.dtype([("best", "<i4"), ("second", "<i4"), ("d2_best", "<i4"), ("d2_second", "<i4")])
 PAIR_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("d2", "<i4"), ("d2_second", "<i4")])
 MATCH_NONE_D2 = 2**31 - 1
+POINT_PAIR_DTYPE = np.dtype([("qx", "<f8"), ("qy", "<f8"), ("tx", "<f8"), ("ty", "<f8")])
+RANSAC_MAX_HYPOTHESES = 65536
+
+
+class Homography(ctypes.Structure):
+    _fields_ = [("h", ctypes.c_double * 9), ("hypothesis", ctypes.c_int32), ("inliers", ctypes.c_int32)]
 
 _lib = None
 
@@ -134,6 +143,7 @@ def lib():
     ip = ctypes.POINTER(ctypes.c_int)
     fp = ctypes.POINTER(ctypes.c_float)
     pp = ctypes.POINTER(Params)
+    hp = ctypes.POINTER(Homography)
     sig = {
         "sift_abi_version": (ctypes.c_int, []),
         "sift_params_default": (ctypes.c_int, [pp]),
@@ -218,6 +228,16 @@ def lib():
         "sift_match_select": (ctypes.c_int, [vp, vp, sz, vp, sz, ctypes.c_double, vp, sz, szp]),
         "sift_match_select_host": (ctypes.c_int, [vp, vp, sz, vp, sz, ctypes.c_double, vp, sz, szp]),
         "sift_last_match_timings": (ctypes.c_int, [vp, dp, dp]),
+        "sift_pair_points_device": (ctypes.c_int, [vp, vp, vp, sz, vp]),
+        "sift_homography_ransac_device": (ctypes.c_int, [vp, vp, sz, sz, ctypes.c_uint64, ctypes.c_double, hp, vp, sz,
+                                                         szp]),
+        "sift_homography_ransac": (ctypes.c_int, [vp, vp, sz, sz, ctypes.c_uint64, ctypes.c_double, hp, vp, sz, szp]),
+        "sift_homography_score": (ctypes.c_int, [vp, vp, sz, vp, sz, ctypes.c_double, vp]),
+        "sift_homography_score_device": (ctypes.c_int, [vp, vp, sz, vp, sz, ctypes.c_double, vp]),
+        "sift_copy_homography_hypotheses": (ctypes.c_int, [vp, vp, vp, sz, szp]),
+        "sift_verify_features": (ctypes.c_int, [vp, vp, vp, sz, sz, ctypes.c_uint64, ctypes.c_double, hp, vp, sz,
+                                                szp]),
+        "sift_last_verify_timings": (ctypes.c_int, [vp, dp, dp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -814,6 +834,86 @@ class Context:
         self._check(self._L.sift_last_match_timings(self._h, ctypes.byref(a), ctypes.byref(b)),
                     "sift_last_match_timings")
         return dict(match_ms=a.value, select_ms=b.value)
+
+    # -- RANSAC homography verification ---------------------------------------
+    @staticmethod
+    def _points(points):
+        p = np.ascontiguousarray(points, dtype=POINT_PAIR_DTYPE)
+        if p.ndim != 1:
+            raise ValueError("points must be POINT_PAIR_DTYPE [n]")
+        return p
+
+    @staticmethod
+    def _model(m, inl, n):
+        return np.array(m.h, dtype=np.float64).reshape(3, 3), int(m.hypothesis), inl[:n]
+
+    def pair_points(self, train_ctx, pairs):
+        """The keypoint positions behind `pairs` (PAIR_DTYPE, this context's
+        records against train_ctx's): POINT_PAIR_DTYPE [n]; an index outside its
+        list gives NaNs (sift_pair_points_device, through torch device buffers)."""
+        import torch
+        pr = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+        n = pr.shape[0]
+        d_pairs = torch.from_numpy(pr.view(np.int32).reshape(n, 4).copy()).cuda()
+        d_pts = torch.zeros((n, 4), dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        self._check(self._L.sift_pair_points_device(self._h, train_ctx._h, d_pairs.data_ptr() if n else None, n,
+                                                    d_pts.data_ptr() if n else None), "sift_pair_points_device")
+        return d_pts.cpu().numpy().reshape(-1).view(POINT_PAIR_DTYPE)
+
+    def ransac_homography(self, points, hypotheses=1024, seed=0, thresh=3.0):
+        """RANSAC homography of POINT_PAIR_DTYPE points (sift_homography_ransac):
+        (H float64 [3, 3], index of the best hypothesis or -1, its inlier
+        indices int32 ascending)."""
+        p = self._points(points)
+        m, n = Homography(), ctypes.c_size_t()
+        inl = np.zeros(max(p.shape[0], 1), dtype=np.int32)
+        self._check(self._L.sift_homography_ransac(self._h, self._ptr(p), p.shape[0], int(hypotheses), int(seed),
+                                                   float(thresh), ctypes.byref(m), self._ptr(inl), inl.shape[0],
+                                                   ctypes.byref(n)), "sift_homography_ransac")
+        return self._model(m, inl, n.value)
+
+    def score_homographies(self, points, H, thresh):
+        """Inlier counts int32 [K] of the caller's matrices H [K, 3, 3] (or
+        [K, 9]) over the points, by the inlier rule alone (sift_homography_score)."""
+        p = self._points(points)
+        h = np.ascontiguousarray(H, dtype=np.float64).reshape(-1, 9)
+        counts = np.zeros(h.shape[0], dtype=np.int32)
+        self._check(self._L.sift_homography_score(self._h, self._ptr(p), p.shape[0], self._ptr(h), h.shape[0],
+                                                  float(thresh), self._ptr(counts)), "sift_homography_score")
+        return counts
+
+    def homography_hypotheses(self):
+        """Every hypothesis of the last RANSAC on this context: (H float64
+        [K, 3, 3], counts int32 [K]; an invalid one is zeros with count -1)."""
+        n = ctypes.c_size_t()
+        self._check(self._L.sift_copy_homography_hypotheses(self._h, None, None, 0, ctypes.byref(n)),
+                    "sift_copy_homography_hypotheses")
+        H = np.zeros((max(n.value, 1), 3, 3), dtype=np.float64)
+        counts = np.zeros(max(n.value, 1), dtype=np.int32)
+        self._check(self._L.sift_copy_homography_hypotheses(self._h, H.ctypes.data_as(ctypes.c_void_p),
+                                                            counts.ctypes.data_as(ctypes.c_void_p), H.shape[0],
+                                                            ctypes.byref(n)), "sift_copy_homography_hypotheses")
+        return H[:n.value], counts[:n.value]
+
+    def verify_features(self, train_ctx, pairs, hypotheses=1024, seed=0, thresh=3.0):
+        """RANSAC homography of the keypoint positions behind `pairs`
+        (PAIR_DTYPE of select_matches between this context and train_ctx), on
+        the device (sift_verify_features): as ransac_homography returns."""
+        pr = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+        m, n = Homography(), ctypes.c_size_t()
+        inl = np.zeros(max(pr.shape[0], 1), dtype=np.int32)
+        self._check(self._L.sift_verify_features(self._h, train_ctx._h, self._ptr(pr), pr.shape[0], int(hypotheses),
+                                                 int(seed), float(thresh), ctypes.byref(m), self._ptr(inl),
+                                                 inl.shape[0], ctypes.byref(n)), "sift_verify_features")
+        return self._model(m, inl, n.value)
+
+    def verify_timings(self):
+        """Device ms of the last RANSAC's hypotheses, scoring and selection."""
+        a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        self._check(self._L.sift_last_verify_timings(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+                    "sift_last_verify_timings")
+        return dict(hypotheses_ms=a.value, score_ms=b.value, select_ms=c.value)
 
     def stream(self):
         return self._L.sift_stream(self._h)
