@@ -1,75 +1,22 @@
 // C ABI of libsift_hip.so (include/sift_hip.h): context, schedule, stage
 // orchestration on one HIP stream.  The stage functions mirror the
 // reference's worker stages (background.js:71 / :258 / :359 / :455).
+// Later stages: sift_api_feature / _match / _verify.hip, over the helpers defined here.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <algorithm>
-#include <cmath>
 #include <cstdlib>
 #include <cstdio>
-#include <cstring>
 #include <map>
 #include <mutex>
-#include <string>
 #include <atomic>
 #include <thread>
-#include <vector>
 
-#include "../../include/sift_hip.h"
-#include "sift_kernels.h"
+#include "sift_ctx.h"
 
 using namespace sift;
 
 namespace {
-
-// Grow-only device buffer, freed with its owner.
-struct DBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  DBuf() = default;
-  DBuf(const DBuf&) = delete;
-  DBuf& operator=(const DBuf&) = delete;
-  ~DBuf() { release(); }
-  hipError_t ensure(size_t need) {
-    if (need <= bytes) return hipSuccess;
-    release();
-    size_t want = need + need / 4 + 256;
-    hipError_t e = hipMalloc(&p, want);
-    if (e == hipSuccess) bytes = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-  template <class T>
-  T* as() const { return reinterpret_cast<T*>(p); }
-};
-
-// Grow-only pinned host buffer (staging of host images and keypoint records), freed with its owner.
-struct HBuf {
-  void* p = nullptr;
-  size_t bytes = 0;
-  HBuf() = default;
-  HBuf(const HBuf&) = delete;
-  HBuf& operator=(const HBuf&) = delete;
-  ~HBuf() { release(); }
-  hipError_t ensure(size_t need) {
-    if (need <= bytes) return hipSuccess;
-    release();
-    size_t want = need + need / 4 + 256;
-    hipError_t e = hipHostMalloc(&p, want, hipHostMallocDefault);
-    if (e == hipSuccess) bytes = want;
-    return e;
-  }
-  void release() {
-    if (p) (void)hipHostFree(p);
-    p = nullptr;
-    bytes = 0;
-  }
-};
 
 // f(i0, i1) over a split of [0, n) into up to `nt` ranges, one per thread
 // (the caller's included).
@@ -135,169 +82,12 @@ double js_round(double x) {
   return (x - f >= 0.5) ? f + 1.0 : f;
 }
 
-enum DogSource { kNone = 0, kNative = 1, kForeign = 2 };
-
 // Device counter slots: 0..31 extrema / refinement counts (see below), then
 // the kept keypoints per (octave, scale) block from kBlk on.
 constexpr int kBlk = 64;
 constexpr int kCntAll = kBlk + kBlkWords;  // per-block counts, block starts, order flag (sift_kernels.h)
 
-// Slots of the pinned count read-backs of the feature and matching stages (sift_ctx::hfeat).
-enum { kFeatOri = 0, kFeatDesc = 1, kFeatPairs = 2, kFeatSlots = 3 };
-
 }  // namespace
-
-struct sift_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  bool own_stream = true;          // false: the stream of another context (sift_ctx_create_shared)
-  std::string err;
-  sift_params p{};
-  int W = 0, H = 0;
-  std::vector<int> dims;           // 2*O
-  std::vector<double> blur, sigma; // O*NS
-  Pyramid P{};
-  GaussPlan gplan[kMaxOctaves]{};  // of P's octaves (setup_geometry)
-  int dog_source = kNone;
-  bool have_gauss = false;
-  bool have_cand = false;
-  size_t n_cand = 0, n_low = 0, n_kp = 0, n_sing = 0, n_exact = 0;
-  size_t n_slots = 0;       // candidate slots (n_cand + entries dropped by the exact pass)
-  bool want_low = false;    // this extrema stage lists the low-contrast extrema
-  bool have_low = false;    // the last extrema stage did (sift_copy_low_contrast)
-  unsigned low_cap = 0;     // slots of the ordered low-contrast list
-  size_t n_low_sure = 0, n_low_late = 0;  // ordered (certain) and exact-pass (late) low-contrast entries
-  unsigned cand_cap = 0;    // capacity of the candidate slot arrays (extrema path)
-  unsigned amb_cap = 0;     // capacity of the ambiguous-key list
-  int slot_cap = 0;         // slots the refinement runs over
-  bool ext_pending = false; // extrema launched, counts not yet read back
-  bool has_keep = false;    // slots carry keep flags
-  bool slots_rows = false;  // slots are the extrema stage's emission (row offsets in rowoff): band order applies
-  bool counters_zeroed = false;  // extrema_prepare zeroed the refinement counters too
-  bool detect_pending = false;   // sift_detect_device_async enqueued, sift_detect_wait not yet called
-  bool begin_pending = false;    // sift_detect_begin_async enqueued, sift_detect_end_async not yet called
-  bool detect_host_img = false;
-  ExtremaLaunch xl{};       // extrema launch state between prepare / scan / finish; xl.G is the bitmap
-                            // geometry of this extrema stage (bitmap_geometry), which every later launch copies
-  int o_first = 0;          // first octave of the pyramid in use (sift_detect_from_seed: > 0)
-  int scan_first = 0;       // first octave the extrema stage scans (>= o_first; sift_detect_from_seed_range)
-  int planes_first = 0;     // first octave with Gaussian / DoG planes (below: only its successor's base)
-  int row0 = 0;             // sift_set_row_origin: input row of the image's first row
-  int xseed_h = 0, xseed_w = 0;  // SIFT_F_EXPORT_NEXT_SEED: the base of octave O
-  bool has_xseed = false;
-  bool has_origins = false; // kp_key holds the candidate key of every keypoint
-  int x_nf = 0;             // leading octaves whose extrema decisions run fused into the Gaussian pass
-  bool x_prepared = false;  // extrema_prepare already ran for this detection (fused octaves)
-  // device memory
-  DBuf img, seeds, gauss, dog, wts;
-  DBuf base0;                                  // materialised octave-0 base (large radii only)
-  DBuf l64;                                    // fp64 Gaussian planes of the large-radius octaves
-  DBuf vsplit;                                 // vertical-sum scratch of the split-pass octaves (one at a time)
-  DBuf seedv;                                  // vertical sums of the seed-only octaves (launch_seed_only)
-  long long vsplit_pi = 0;                     // ... doubles per image of a batch
-  std::vector<double> wts_host;                // taps last uploaded to wts
-  // Taps of the deepest schedule built so far (setup_geometry): per-(octave,
-  // scale) sigma, the padded tap vector, its length after each octave, and
-  // every scale's radius and tap offset.  Sigma does not depend on the octave
-  // count, so a schedule whose sigmas are a prefix of these reuses a prefix
-  // of the taps instead of ~3 K exp() per call (8K O6 S5: ~35 us).
-  struct TapCache {
-    int NS = 0;
-    std::vector<double> sigma, w;
-    std::vector<size_t> oct_end;
-    std::vector<int> rad, wofs;
-  } taps;
-  DBuf bitmap, rowcount, rowoff, amb_keys;     // extrema scan
-  DBuf ambbitmap;                              // ambiguous words (k_exact_words)
-  bool x_words = false;                        // this extrema stage lists ambiguous words, not keys
-  DBuf cand_key, cand_val, cand_keep;          // ordered candidates
-  DBuf lowbitmap, lowrowcount, lowrowoff;      // low-contrast list (SIFT_F_LOW_CONTRAST_LIST)
-  DBuf low_key, low_val, late_key, late_val;
-  DBuf keep, pos;                              // keypoint compaction
-  DBuf keep_tile;                              // ... its per-tile counts (launch_keep_compact)
-  DBuf band_cnt, band_first, band_start, perm;  // refinement band order
-  DBuf status, kp_tmp, kp, uncertain;          // refinement
-  DBuf kp_soa;                                 // keypoint field arrays for a DMA into registered host arrays
-  DBuf xseed, kp_key;                          // next-octave base, keypoint origins
-  DBuf merge_tab;                              // sift_merge_keypoint_blocks_device tables
-  // orientation / descriptor stages (sift_feature.hip)
-  bool have_kp = false;                        // a refinement has settled on this pyramid: kp / n_kp are its list
-  bool have_ori = false, have_desc = false;    // ori / desc hold the records of that list
-  size_t n_ori = 0, n_desc_ok = 0;             // records, described records
-  DBuf ori_count, ori_off, ori_mask, ori_theta;  // per keypoint: peaks, their exclusive scan, bins, angles
-  DBuf ori, desc, desc_ok, desc_n;             // records, 128 bytes each, described flags, described count
-  HBuf hfeat;                                  // pinned: kFeatSlots count read-backs (kFeatOri ..)
-  hipEvent_t ev_f[4]{};                        // around the orientation stage [0, 1] and the descriptor stage [2, 3]
-  double orient_ms = 0, describe_ms = 0;
-  // descriptor matching (sift_match.hip)
-  DBuf m_qs, m_ts, m_qn, m_kb;                 // shifted, padded query / train rows; query norms, train key bases
-  DBuf m_part, m_out;                          // per-split partial records; the last match's records
-  DBuf m_in_q, m_in_t, m_in_qm, m_in_tm;       // host-form inputs (sift_match)
-  DBuf m_fwd, m_rev, m_flag, m_off, m_pairs;   // selection: host-form inputs, flags, their scan, host-form pairs
-  size_t n_match = 0;                          // records in m_out
-  bool have_match = false;
-  hipEvent_t ev_m[4]{};                        // around the match [0, 1] and the selection [2, 3]
-  double match_ms = 0, select_ms = 0;
-  // homography verification (sift_verify.hip)
-  DBuf v_H, v_valid, v_cnt, v_model;           // the last RANSAC's hypotheses, valid flags, counts; its model record
-  DBuf v_flag, v_off;                          // inlier flags of the best model, their scan
-  DBuf v_in_pts, v_in_H, v_in_cnt, v_pairs;    // host-form inputs and counts (sift_homography_score, sift_verify_features)
-  DBuf v_pts, v_inl;                           // gathered points (sift_verify_features); host-form inlier list
-  HBuf hver;                                   // pinned: the model record, then the inlier count
-  size_t n_hyp = 0;                            // hypotheses in v_H / v_cnt
-  bool have_ransac = false;
-  hipEvent_t ev_v[6]{};                        // around the hypotheses [0, 1], the scoring [2, 3], the selection [4, 5]
-  double v_hyp_ms = 0, v_score_ms = 0, v_select_ms = 0;
-  DBuf counters, temp;
-  DBuf rgba, alpha, display, mm_parts;         // image products (sift_image.hip)
-  unsigned* h_counters = nullptr;              // pinned mirror of counters (+ per-block keypoint counts at kBlk)
-  int own_lo = -1, own_hi = -1;                // sift_set_owned_rows
-  std::vector<long long> blk_counts;           // kept keypoints per (octave, scale) of the last refinement
-  HBuf himg, hkp;                  // pinned staging: host images in, keypoint records out
-  hipEvent_t ev_himg = nullptr;    // the DMA out of himg is done (himg may be refilled)
-  HBuf hpl;                        // pinned staging of plane reads: two halves, double-buffered
-  hipEvent_t ev_pl[2] = {nullptr, nullptr};
-  hipEvent_t ev[8]{};
-  hipEvent_t ev_heavy = nullptr;  // after the last bandwidth-heavy kernel of a detection (sift_order_after)
-  hipEvent_t ev_go[kMaxOctaves]{}; // after octave o's Gaussian+DoG launch (per-octave timings)
-  sift_timings tm{};
-  std::vector<double> oct_ms;      // per-octave Gaussian+DoG launch time of the last build
-  std::vector<std::string> pass_kn; // per-octave pass kernels of the last build (sift_last_pass_kernels)
-
-  // The buffers free themselves; the caller has made `device` current and the stream is idle.
-  ~sift_ctx() {
-    for (auto& e : ev)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_go)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_f)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_m)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_v)
-      if (e) (void)hipEventDestroy(e);
-    for (auto& e : ev_pl)
-      if (e) (void)hipEventDestroy(e);
-    if (ev_heavy) (void)hipEventDestroy(ev_heavy);
-    if (ev_himg) (void)hipEventDestroy(ev_himg);
-    if (h_counters) (void)hipHostFree(h_counters);
-    if (stream && own_stream) (void)hipStreamDestroy(stream);
-  }
-};
-
-#define HIPCHK(call)                                                                        \
-  do {                                                                                      \
-    hipError_t e_ = (call);                                                                 \
-    if (e_ != hipSuccess) {                                                                 \
-      ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
-      return SIFT_E_HIP;                                                                    \
-    }                                                                                       \
-  } while (0)
-
-static int set_err(sift_ctx* ctx, int code, const std::string& msg) {
-  if (ctx) ctx->err = msg;
-  return code;
-}
 
 static int check_params(const sift_params* p) {
   if (!p) return SIFT_E_ARG;
@@ -328,15 +118,14 @@ static bool host_registered(const void* p, size_t bytes) {
   return a >= it->first && a + bytes <= it->first + it->second;
 }
 
-static hipError_t d2h_staged(sift_ctx* ctx, void* dst, const void* src, size_t bytes) {
+hipError_t sift::d2h_staged(sift_ctx* ctx, void* dst, const void* src, size_t bytes) {
   constexpr size_t kChunk = (size_t)8 << 20;
   if (bytes < ((size_t)1 << 20) || host_registered(dst, bytes)) {  // small or page-locked: one DMA straight into it
     hipError_t e = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream);
     return e != hipSuccess ? e : hipStreamSynchronize(ctx->stream);
   }
   hipError_t e = ctx->hpl.ensure(2 * kChunk);
-  for (int i = 0; i < 2 && e == hipSuccess; ++i)
-    if (!ctx->ev_pl[i]) e = hipEventCreateWithFlags(&ctx->ev_pl[i], hipEventDisableTiming);
+  if (e == hipSuccess) e = ctx->ev_pl.ensure();
   if (e != hipSuccess) return e;
   char* half[2] = {(char*)ctx->hpl.p, (char*)ctx->hpl.p + kChunk};
   const size_t n = (bytes + kChunk - 1) / kChunk;
@@ -440,12 +229,13 @@ static int ctx_create(int device, sift_ctx* share, sift_ctx** out) {
       (share ? (ctx->stream = share->stream, false)
              : hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) ||
       hipHostMalloc((void**)&ctx->h_counters, kCntAll * sizeof(unsigned), hipHostMallocDefault) != hipSuccess ||
+      ctx->hscratch.ensure(sizeof(StageScratch)) != hipSuccess ||
       ctx->counters.ensure(kCntAll * sizeof(unsigned)) != hipSuccess) {
     delete ctx;
     return SIFT_E_HIP;
   }
-  for (auto& e : ctx->ev) (void)hipEventCreate(&e);
-  for (auto& e : ctx->ev_go) (void)hipEventCreate(&e);
+  (void)ctx->ev.ensure();
+  (void)ctx->ev_go.ensure();
   (void)hipEventCreateWithFlags(&ctx->ev_heavy, hipEventDisableTiming);
   *out = ctx;
   return SIFT_OK;
@@ -828,7 +618,7 @@ static int build_common(sift_ctx* ctx, const float* img_host, const float* img_d
   ctx->dog_source = kNative;
   ctx->have_gauss = keep_gauss;
   ctx->have_cand = false;
-  ctx->have_kp = ctx->have_ori = ctx->have_desc = false;
+  ctx->have_kp = ctx->feat.have_ori = ctx->feat.have_desc = false;
   ctx->has_xseed = xseed;
   return SIFT_OK;
 }
@@ -934,7 +724,7 @@ static int finish_load(sift_ctx* ctx, bool have_gauss) {
   ctx->planes_first = 0;
   ctx->have_gauss = have_gauss;
   ctx->have_cand = false;
-  ctx->have_kp = ctx->have_ori = ctx->have_desc = false;
+  ctx->have_kp = ctx->feat.have_ori = ctx->feat.have_desc = false;
   HIPCHK(hipStreamSynchronize(ctx->stream));
   return SIFT_OK;
 }
@@ -1110,13 +900,48 @@ static int extrema_scan(sift_ctx* ctx, int o0, int o1, hipStream_t st) {
 }
 
 // out = the exclusive prefix sums of in[0 .. n), on the context stream (scratch: ctx->temp).
-static hipError_t exclusive_sum(sift_ctx* ctx, unsigned* in, unsigned* out, int n) {
+hipError_t sift::exclusive_sum(sift_ctx* ctx, unsigned* in, unsigned* out, int n) {
   size_t tb = 0;
   hipError_t e = hipcub::DeviceScan::ExclusiveSum(nullptr, tb, in, out, n, ctx->stream);
   if (e == hipSuccess) e = ctx->temp.ensure(tb);
   if (e != hipSuccess) return e;
   tb = ctx->temp.bytes;
   return hipcub::DeviceScan::ExclusiveSum(ctx->temp.p, tb, in, out, n, ctx->stream);
+}
+
+// ---- What the feature, match and verify stages share (sift_ctx.h) ----------
+bool sift::count_ok(size_t n) { return n < (size_t)0x7fffffff; }  // a scan over n + 1 items fits an int
+
+// Milliseconds between two completed events, 0 when the query fails.
+double sift::event_ms(hipEvent_t a, hipEvent_t b) {
+  float t = 0;
+  return hipEventElapsedTime(&t, a, b) == hipSuccess ? t : 0.0;
+}
+
+// Host bytes into a context buffer, queued on the stream (nothing for bytes == 0 or src == nullptr).
+int sift::h2d_buffer(sift_ctx* ctx, DBuf& b, const void* src, size_t bytes) {
+  if (!src || !bytes) return SIFT_OK;
+  HIPCHK(b.ensure(bytes));
+  HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return SIFT_OK;
+}
+
+// The count half of an ordered, sort-free selection: offsets = the exclusive scan of counts[0 .. n] (counts[n] is a
+// zero), and *total = offsets[n] read back through the pinned word, which sizes the output of the emit kernel that
+// follows; the stream is idle on return.  counts == nullptr: the read-back of offsets[n] alone.
+int sift::ordered_total(sift_ctx* ctx, unsigned* counts, unsigned* offsets, int n, unsigned* total) {
+  unsigned* h = &static_cast<StageScratch*>(ctx->hscratch.p)->word;
+  if (counts) HIPCHK(exclusive_sum(ctx, counts, offsets, n + 1));
+  HIPCHK(hipMemcpyAsync(h, offsets + n, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(hipStreamSynchronize(ctx->stream));
+  *total = *h;
+  return SIFT_OK;
+}
+
+// No detection is in flight and the context holds a keypoint list [, its orientation records [, their descriptors]].
+bool sift::stage_has(const sift_ctx* c, StageNeed need) {
+  return !c->detect_pending && !c->begin_pending && c->have_kp && (need < kNeedOri || c->feat.have_ori) &&
+         (need < kNeedDesc || c->feat.have_desc);
 }
 
 // One ordered list from a bitmap of this extrema stage's geometry: the row
@@ -1270,7 +1095,7 @@ static int refine_enqueue(sift_ctx* ctx) {
   ctx->counters_zeroed = false;
   ctx->n_kp = 0;
   ctx->n_sing = 0;
-  ctx->have_kp = ctx->have_ori = ctx->have_desc = false;
+  ctx->have_kp = ctx->feat.have_ori = ctx->feat.have_desc = false;
   if (cap > 0) {
     RefineLaunch R{};
     R.cand_key = ctx->cand_key.as<unsigned>();
@@ -1356,7 +1181,7 @@ static int refine_settle(sift_ctx* ctx) {
   ctx->n_kp = cap > 0 ? h[kCntKp] : 0;
   ctx->n_sing = h[kCntSing];
   ctx->have_kp = true;
-  ctx->have_ori = ctx->have_desc = false;
+  ctx->feat.have_ori = ctx->feat.have_desc = false;
   ctx->blk_counts.assign((size_t)std::max(1, ctx->P.nimg) * ctx->P.O * ctx->P.S, 0);
   if (cap > 0)
     for (size_t b = 0; b < ctx->blk_counts.size(); ++b) ctx->blk_counts[b] = h[kBlk + b];
@@ -1490,10 +1315,8 @@ int sift_set_candidates(sift_ctx* ctx, const sift_extremum* cand, size_t n) {
   HIPCHK(hipSetDevice(ctx->device));
   HIPCHK(ctx->cand_key.ensure(std::max<size_t>(n, 1) * sizeof(unsigned)));
   HIPCHK(ctx->cand_val.ensure(std::max<size_t>(n, 1) * sizeof(double)));
-  if (n) {
-    HIPCHK(hipMemcpyAsync(ctx->cand_key.p, keys.data(), n * sizeof(unsigned), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipMemcpyAsync(ctx->cand_val.p, vals.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-  }
+  if (int rc = h2d_buffer(ctx, ctx->cand_key, keys.data(), n * sizeof(unsigned))) return rc;
+  if (int rc = h2d_buffer(ctx, ctx->cand_val, vals.data(), n * sizeof(double))) return rc;
   const unsigned n32 = (unsigned)n;
   HIPCHK(hipMemcpyAsync(ctx->counters.as<unsigned>() + kCntN, &n32, sizeof(unsigned), hipMemcpyHostToDevice,
                         ctx->stream));
@@ -2004,654 +1827,6 @@ int sift_plane_image(sift_ctx* ctx, int kind, int octave, int scale, int mode, d
 int sift_plane_image_device(sift_ctx* ctx, int kind, int octave, int scale, int mode, double coefficient,
                             uint8_t* d_rgba, size_t cap_bytes) {
   return plane_image_common(ctx, kind, octave, scale, mode, coefficient, d_rgba, cap_bytes, false);
-}
-
-// ---- Orientation assignment and descriptors (sift_feature.hip) ------------
-static_assert(sizeof(sift_orientation) == 16 && sizeof(Orientation) == 16, "16-byte orientation records");
-static_assert(kOriBins == SIFT_ORI_BINS && kOriSmooth == SIFT_ORI_SMOOTH && kOriMaxPeaks == SIFT_ORI_MAX_PEAKS &&
-                  kOriLambda == SIFT_ORI_LAMBDA && kOriPeakRatio == SIFT_ORI_PEAK_RATIO,
-              "orientation constants of include/sift_hip.h");
-static_assert(kDescOri == SIFT_DESC_ORI && kDescBytes == SIFT_DESC_BYTES && kDescLambda == SIFT_DESC_LAMBDA &&
-                  kDescCap == SIFT_DESC_CAP && SIFT_DESC_CELLS * SIFT_DESC_CELLS * SIFT_DESC_ORI == SIFT_DESC_BYTES,
-              "descriptor constants of include/sift_hip.h");
-
-// What the two stages need of the pyramid, whoever supplies the keypoints
-// (sift_set_keypoints needs no more): one whole image whose octaves all have
-// Gaussian planes.
-static int check_feature_planes(sift_ctx* ctx) {
-  if (ctx->detect_pending || ctx->begin_pending || ctx->dog_source == kNone)
-    return set_err(ctx, SIFT_E_STATE, "no pyramid: build or load one first");
-  if (ctx->P.nimg > 1) return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors of a batch");
-  if (ctx->row0 != 0 || ctx->own_lo >= 0)
-    return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors with a row origin or owned rows");
-  if (ctx->planes_first > ctx->o_first)
-    return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors of a seed-range detection");
-  if (!ctx->have_gauss) return set_err(ctx, SIFT_E_STATE, "Gaussian planes not materialised");
-  return SIFT_OK;
-}
-
-// ... and of the context: a settled refinement (or sift_set_keypoints) on that pyramid.
-static int check_features(sift_ctx* ctx) {
-  if (ctx->detect_pending || ctx->begin_pending || !ctx->have_kp)
-    return set_err(ctx, SIFT_E_STATE, "no refinement: run sift_refine or a detection first");
-  if (int rc = check_feature_planes(ctx)) return rc;
-  for (auto& e : ctx->ev_f)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  HIPCHK(ctx->hfeat.ensure(kFeatSlots * sizeof(unsigned)));
-  return SIFT_OK;
-}
-
-int sift_orient(sift_ctx* ctx, sift_orientation* out, size_t cap, size_t* n_out) {
-  if (!ctx) return SIFT_E_ARG;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (int rc = check_features(ctx)) return rc;
-  if (!ctx->have_ori) {
-    const int n = (int)ctx->n_kp;
-    ctx->have_desc = false;
-    ctx->n_ori = 0;
-    ctx->orient_ms = 0;
-    if (n > 0) {
-      HIPCHK(ctx->ori_count.ensure((size_t)(n + 1) * sizeof(unsigned)));
-      HIPCHK(ctx->ori_off.ensure((size_t)(n + 1) * sizeof(unsigned)));
-      HIPCHK(ctx->ori_mask.ensure((size_t)n * sizeof(unsigned long long)));
-      HIPCHK(ctx->ori_theta.ensure((size_t)n * kOriMaxPeaks * sizeof(double)));
-      unsigned* h_n = (unsigned*)ctx->hfeat.p + kFeatOri;
-      HIPCHK(hipEventRecord(ctx->ev_f[0], ctx->stream));
-      HIPCHK(launch_orient(ctx->P, ctx->gauss.as<float>(), ctx->planes_first, ctx->kp.as<Keypoint>(), n,
-                           ctx->ori_count.as<unsigned>(), ctx->ori_mask.as<unsigned long long>(),
-                           ctx->ori_theta.as<double>(), ctx->stream));
-      HIPCHK(exclusive_sum(ctx, ctx->ori_count.as<unsigned>(), ctx->ori_off.as<unsigned>(), n + 1));
-      HIPCHK(hipMemcpyAsync(h_n, ctx->ori_off.as<unsigned>() + n, sizeof(unsigned), hipMemcpyDeviceToHost,
-                            ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));  // the record count sizes the record buffer
-      const unsigned total = *h_n;
-      HIPCHK(ctx->ori.ensure((size_t)std::max(total, 1u) * sizeof(Orientation)));
-      HIPCHK(launch_orient_emit(ctx->ori_off.as<unsigned>(), ctx->ori_mask.as<unsigned long long>(),
-                                ctx->ori_theta.as<double>(), n, total, ctx->ori.as<Orientation>(), ctx->stream));
-      HIPCHK(hipEventRecord(ctx->ev_f[1], ctx->stream));
-      HIPCHK(hipEventSynchronize(ctx->ev_f[1]));
-      float t = 0;
-      if (hipEventElapsedTime(&t, ctx->ev_f[0], ctx->ev_f[1]) == hipSuccess) ctx->orient_ms = t;
-      ctx->n_ori = total;
-    }
-    ctx->have_ori = true;
-  }
-  if (n_out) *n_out = ctx->n_ori;
-  if (!out) return SIFT_OK;
-  if (cap < ctx->n_ori) return set_err(ctx, SIFT_E_CAPACITY, "orientation buffer too small");
-  if (ctx->n_ori) {
-    HIPCHK(hipMemcpyAsync(out, ctx->ori.p, ctx->n_ori * sizeof(sift_orientation), hipMemcpyDeviceToHost,
-                          ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  return SIFT_OK;
-}
-
-int sift_describe(sift_ctx* ctx, uint8_t* desc, uint8_t* described, size_t cap, size_t* n_out, size_t* n_described) {
-  if (!ctx) return SIFT_E_ARG;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (int rc = check_features(ctx)) return rc;
-  if (!ctx->have_ori) return set_err(ctx, SIFT_E_STATE, "no orientations: run sift_orient first");
-  const size_t n = ctx->n_ori;
-  if (!ctx->have_desc) {
-    ctx->n_desc_ok = 0;
-    ctx->describe_ms = 0;
-    if (n > 0) {
-      HIPCHK(ctx->desc.ensure(n * kDescBytes));
-      HIPCHK(ctx->desc_ok.ensure(n));
-      HIPCHK(ctx->desc_n.ensure(sizeof(unsigned)));
-      unsigned* h_n = (unsigned*)ctx->hfeat.p + kFeatDesc;
-      HIPCHK(hipEventRecord(ctx->ev_f[2], ctx->stream));
-      HIPCHK(hipMemsetAsync(ctx->desc_n.p, 0, sizeof(unsigned), ctx->stream));
-      HIPCHK(launch_describe(ctx->P, ctx->gauss.as<float>(), ctx->planes_first, ctx->kp.as<Keypoint>(),
-                             ctx->ori.as<Orientation>(), (int)n, ctx->desc.as<unsigned char>(),
-                             ctx->desc_ok.as<unsigned char>(), ctx->desc_n.as<unsigned>(), ctx->stream));
-      HIPCHK(hipEventRecord(ctx->ev_f[3], ctx->stream));
-      HIPCHK(hipMemcpyAsync(h_n, ctx->desc_n.p, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-      HIPCHK(hipStreamSynchronize(ctx->stream));
-      float t = 0;
-      if (hipEventElapsedTime(&t, ctx->ev_f[2], ctx->ev_f[3]) == hipSuccess) ctx->describe_ms = t;
-      ctx->n_desc_ok = *h_n;
-    }
-    ctx->have_desc = true;
-  }
-  if (n_out) *n_out = n;
-  if (n_described) *n_described = ctx->n_desc_ok;
-  if (!desc) return described ? set_err(ctx, SIFT_E_ARG, "described without desc") : SIFT_OK;
-  if (cap < n) return set_err(ctx, SIFT_E_CAPACITY, "descriptor buffer too small");
-  if (n) {
-    HIPCHK(d2h_staged(ctx, desc, ctx->desc.p, n * kDescBytes));
-    if (described) HIPCHK(d2h_staged(ctx, described, ctx->desc_ok.p, n));
-  }
-  return SIFT_OK;
-}
-
-int sift_device_features(sift_ctx* ctx, const sift_orientation** d_ori, const uint8_t** d_desc,
-                         const uint8_t** d_described, size_t* n) {
-  if (!ctx || !n) return SIFT_E_ARG;
-  if (!ctx->have_kp || !ctx->have_ori || !ctx->have_desc)
-    return set_err(ctx, SIFT_E_STATE, "no features: run sift_orient and sift_describe first");
-  if (d_ori) *d_ori = ctx->ori.as<const sift_orientation>();
-  if (d_desc) *d_desc = ctx->desc.as<const uint8_t>();
-  if (d_described) *d_described = ctx->desc_ok.as<const uint8_t>();
-  *n = ctx->n_ori;
-  return SIFT_OK;
-}
-
-int sift_last_feature_timings(sift_ctx* ctx, double* orient_ms, double* describe_ms) {
-  if (!ctx) return SIFT_E_ARG;
-  if (orient_ms) *orient_ms = ctx->orient_ms;
-  if (describe_ms) *describe_ms = ctx->describe_ms;
-  return SIFT_OK;
-}
-
-int sift_set_keypoints(sift_ctx* ctx, const sift_keypoint* kp, size_t n) {
-  if (!ctx || (!kp && n)) return SIFT_E_ARG;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (int rc = check_feature_planes(ctx)) return rc;
-  if (n >= (size_t)0x7fffffff) return set_err(ctx, SIFT_E_ARG, "too many keypoints");  // the scan runs over n + 1
-  const Pyramid& P = ctx->P;
-  for (size_t i = 0; i < n; ++i) {
-    if (kp[i].octave < ctx->planes_first || kp[i].octave >= P.O)
-      return set_err(ctx, SIFT_E_ARG, "keypoint octave out of range");
-    if (kp[i].scale_level < 0 || kp[i].scale_level >= P.NS)
-      return set_err(ctx, SIFT_E_ARG, "keypoint scale_level out of range");
-  }
-  HIPCHK(ctx->kp.ensure(std::max<size_t>(n, 1) * sizeof(Keypoint)));
-  if (n) {
-    HIPCHK(hipMemcpyAsync(ctx->kp.p, kp, n * sizeof(sift_keypoint), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  ctx->n_kp = n;
-  ctx->have_kp = true;
-  ctx->have_ori = ctx->have_desc = false;
-  ctx->n_ori = ctx->n_desc_ok = 0;
-  // nothing of the refinement this list replaces is served afterwards
-  ctx->n_sing = 0;
-  ctx->has_origins = false;
-  ctx->blk_counts.clear();
-  ctx->tm.refine_ms = 0;
-  ctx->orient_ms = ctx->describe_ms = 0;
-  return SIFT_OK;
-}
-
-int sift_set_orientations(sift_ctx* ctx, const sift_orientation* rec, size_t n) {
-  if (!ctx || (!rec && n)) return SIFT_E_ARG;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (int rc = check_features(ctx)) return rc;
-  if (n > (size_t)0x7fffffff) return set_err(ctx, SIFT_E_ARG, "too many orientation records");
-  for (size_t i = 0; i < n; ++i) {
-    if (rec[i].keypoint < 0 || (size_t)rec[i].keypoint >= ctx->n_kp)
-      return set_err(ctx, SIFT_E_ARG, "orientation record of no keypoint");
-    if (rec[i].bin < 0 || rec[i].bin >= kOriBins) return set_err(ctx, SIFT_E_ARG, "orientation bin out of range");
-    if (!(rec[i].theta >= 0.0 && rec[i].theta < 2.0 * M_PI))  // a NaN fails both
-      return set_err(ctx, SIFT_E_ARG, "theta outside [0, 2 pi)");
-  }
-  HIPCHK(ctx->ori.ensure(std::max<size_t>(n, 1) * sizeof(Orientation)));
-  if (n) {
-    HIPCHK(hipMemcpyAsync(ctx->ori.p, rec, n * sizeof(sift_orientation), hipMemcpyHostToDevice, ctx->stream));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-  }
-  ctx->n_ori = n;
-  ctx->have_ori = true;
-  ctx->have_desc = false;
-  ctx->n_desc_ok = 0;
-  ctx->orient_ms = ctx->describe_ms = 0;
-  return SIFT_OK;
-}
-
-// ---- Descriptor matching (sift_match.hip) ---------------------------------
-static_assert(sizeof(struct sift_match) == 16 && sizeof(Match) == 16 && sizeof(sift_match_pair) == 16 &&
-                  sizeof(MatchPair) == 16,
-              "16-byte match records");
-static_assert(SIFT_MATCH_NONE_D2 == INT32_MAX && kDescBytes == SIFT_DESC_BYTES, "match constants of include/sift_hip.h");
-
-static bool match_count_ok(size_t n) { return n < (size_t)0x7fffffff; }
-static bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-static int match_events(sift_ctx* ctx) {
-  for (auto& e : ctx->ev_m)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  HIPCHK(ctx->hfeat.ensure(kFeatSlots * sizeof(unsigned)));
-  return SIFT_OK;
-}
-
-// The match of validated device arrays into d_out (n_query records), timed and complete on return.
-static int match_run(sift_ctx* ctx, const uint8_t* d_q, const uint8_t* d_qm, int nq, const uint8_t* d_t,
-                     const uint8_t* d_tm, int nt, Match* d_out) {
-  if (int rc = match_events(ctx)) return rc;
-  ctx->match_ms = 0;
-  if (nq == 0) return SIFT_OK;
-  const MatchSplit sp = match_split(nq, nt);
-  Match* part = d_out;
-  if (nt > 0) {
-    const size_t qrows = (size_t)match_query_rows(nq), trows = (size_t)match_train_rows(nt);
-    HIPCHK(ctx->m_qs.ensure(qrows * kDescBytes));
-    HIPCHK(ctx->m_qn.ensure(qrows * sizeof(int)));
-    HIPCHK(ctx->m_ts.ensure(trows * kDescBytes));
-    HIPCHK(ctx->m_kb.ensure(trows * sizeof(int)));
-    if (sp.splits > 1) {
-      HIPCHK(ctx->m_part.ensure((size_t)sp.splits * nq * sizeof(Match)));
-      part = ctx->m_part.as<Match>();
-    }
-    HIPCHK(hipEventRecord(ctx->ev_m[0], ctx->stream));
-    HIPCHK(launch_match_prep(d_q, d_qm, nq, (long long)qrows, 0, ctx->m_qs.as<unsigned char>(), ctx->m_qn.as<int>(),
-                             ctx->stream));
-    HIPCHK(launch_match_prep(d_t, d_tm, nt, (long long)trows, 1, ctx->m_ts.as<unsigned char>(), ctx->m_kb.as<int>(),
-                             ctx->stream));
-    HIPCHK(launch_match(ctx->m_qs.as<unsigned char>(), ctx->m_qn.as<int>(), nq, ctx->m_ts.as<unsigned char>(),
-                        ctx->m_kb.as<int>(), nt, part, ctx->stream));
-    if (sp.splits > 1) HIPCHK(launch_match_merge(part, sp.splits, nq, d_out, ctx->stream));
-  } else {
-    HIPCHK(hipEventRecord(ctx->ev_m[0], ctx->stream));
-    HIPCHK(launch_match_merge(nullptr, 0, nq, d_out, ctx->stream));  // no train rows: every neighbour missing
-  }
-  HIPCHK(hipEventRecord(ctx->ev_m[1], ctx->stream));
-  HIPCHK(hipEventSynchronize(ctx->ev_m[1]));
-  float t = 0;
-  if (hipEventElapsedTime(&t, ctx->ev_m[0], ctx->ev_m[1]) == hipSuccess) ctx->match_ms = t;
-  return SIFT_OK;
-}
-
-int sift_match_device(sift_ctx* ctx, const uint8_t* d_query, const uint8_t* d_query_mask, size_t n_query,
-                      const uint8_t* d_train, const uint8_t* d_train_mask, size_t n_train, struct sift_match* d_out) {
-  if (!ctx) return SIFT_E_ARG;
-  if (!match_count_ok(n_query) || !match_count_ok(n_train)) return set_err(ctx, SIFT_E_ARG, "too many descriptors");
-  if ((n_query && (!d_query || !d_out)) || (n_train && !d_train))
-    return set_err(ctx, SIFT_E_ARG, "null descriptor or result pointer");
-  if (!aligned16(d_query) || !aligned16(d_train)) return set_err(ctx, SIFT_E_ARG, "descriptors not 16-byte aligned");
-  HIPCHK(hipSetDevice(ctx->device));
-  return match_run(ctx, d_query, d_query_mask, (int)n_query, d_train, d_train_mask, (int)n_train,
-                   reinterpret_cast<Match*>(d_out));
-}
-
-// Host bytes into a context buffer (nothing for bytes == 0 or src == nullptr).
-static int match_upload(sift_ctx* ctx, DBuf& b, const void* src, size_t bytes) {
-  if (!src || !bytes) return SIFT_OK;
-  HIPCHK(b.ensure(bytes));
-  HIPCHK(hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return SIFT_OK;
-}
-
-int sift_match(sift_ctx* ctx, const uint8_t* query, const uint8_t* query_mask, size_t n_query, const uint8_t* train,
-               const uint8_t* train_mask, size_t n_train, struct sift_match* out) {
-  if (!ctx) return SIFT_E_ARG;
-  if (!match_count_ok(n_query) || !match_count_ok(n_train)) return set_err(ctx, SIFT_E_ARG, "too many descriptors");
-  if ((n_query && (!query || !out)) || (n_train && !train))
-    return set_err(ctx, SIFT_E_ARG, "null descriptor or result pointer");
-  HIPCHK(hipSetDevice(ctx->device));
-  if (n_query == 0) {  // the last match has no records
-    ctx->match_ms = 0;
-    ctx->n_match = 0;
-    ctx->have_match = true;
-    return SIFT_OK;
-  }
-  if (int rc = match_upload(ctx, ctx->m_in_q, query, n_query * kDescBytes)) return rc;
-  if (int rc = match_upload(ctx, ctx->m_in_qm, query_mask, n_query)) return rc;
-  if (int rc = match_upload(ctx, ctx->m_in_t, train, n_train * kDescBytes)) return rc;
-  if (int rc = match_upload(ctx, ctx->m_in_tm, n_train ? train_mask : nullptr, n_train)) return rc;
-  HIPCHK(ctx->m_out.ensure(n_query * sizeof(Match)));
-  ctx->have_match = false;
-  int rc = match_run(ctx, ctx->m_in_q.as<uint8_t>(), query_mask ? ctx->m_in_qm.as<uint8_t>() : nullptr, (int)n_query,
-                     ctx->m_in_t.as<uint8_t>(), n_train && train_mask ? ctx->m_in_tm.as<uint8_t>() : nullptr,
-                     (int)n_train, ctx->m_out.as<Match>());
-  if (rc) return rc;
-  ctx->n_match = n_query;
-  ctx->have_match = true;
-  HIPCHK(d2h_staged(ctx, out, ctx->m_out.p, n_query * sizeof(Match)));
-  return SIFT_OK;
-}
-
-int sift_match_features(sift_ctx* ctx, sift_ctx* train_ctx, struct sift_match* out, size_t cap, size_t* n_out) {
-  if (!ctx || !train_ctx) return SIFT_E_ARG;
-  for (sift_ctx* c : {ctx, train_ctx})
-    if (c->detect_pending || c->begin_pending || !c->have_kp || !c->have_ori || !c->have_desc)
-      return set_err(ctx, SIFT_E_STATE, "no descriptors: run sift_orient and sift_describe on both contexts first");
-  if (ctx->device != train_ctx->device) return set_err(ctx, SIFT_E_ARG, "contexts on different devices");
-  HIPCHK(hipSetDevice(ctx->device));
-  const size_t nq = ctx->n_ori, nt = train_ctx->n_ori;  // both below 2^31 - 1 (sift_orient's scan, sift_set_orientations)
-  if (!match_count_ok(nq) || !match_count_ok(nt)) return set_err(ctx, SIFT_E_ARG, "too many descriptors");
-  HIPCHK(ctx->m_out.ensure(std::max<size_t>(nq, 1) * sizeof(Match)));
-  ctx->have_match = false;
-  int rc = match_run(ctx, ctx->desc.as<uint8_t>(), ctx->desc_ok.as<uint8_t>(), (int)nq, train_ctx->desc.as<uint8_t>(),
-                     train_ctx->desc_ok.as<uint8_t>(), (int)nt, ctx->m_out.as<Match>());
-  if (rc) return rc;
-  ctx->n_match = nq;
-  ctx->have_match = true;
-  if (n_out) *n_out = nq;
-  if (!out) return SIFT_OK;
-  if (cap < nq) return set_err(ctx, SIFT_E_CAPACITY, "match buffer too small");
-  if (nq) HIPCHK(d2h_staged(ctx, out, ctx->m_out.p, nq * sizeof(Match)));
-  return SIFT_OK;
-}
-
-int sift_device_matches(sift_ctx* ctx, const struct sift_match** d_match, size_t* n) {
-  if (!ctx || !d_match || !n) return SIFT_E_ARG;
-  if (!ctx->have_match) return set_err(ctx, SIFT_E_STATE, "no match: run sift_match or sift_match_features first");
-  *d_match = ctx->m_out.as<const struct sift_match>();
-  *n = ctx->n_match;
-  return SIFT_OK;
-}
-
-static int select_check(sift_ctx* ctx, const void* fwd, size_t n_query, size_t n_train, double ratio) {
-  if (!match_count_ok(n_query) || !match_count_ok(n_train)) return set_err(ctx, SIFT_E_ARG, "too many records");
-  if (n_query && !fwd) return set_err(ctx, SIFT_E_ARG, "null match records");
-  if (!(ratio <= 0.0) && !(std::isfinite(ratio) && ratio < 1.0))  // a NaN fails both
-    return set_err(ctx, SIFT_E_ARG, "ratio must be below 1, or <= 0 for no ratio test");
-  return SIFT_OK;
-}
-
-// Flags, their scan and the pair count of validated device records (nq > 0); starts the selection's timing.
-static int select_count(sift_ctx* ctx, const Match* fwd, int nq, const Match* rev, int nt, double ratio,
-                        unsigned* total) {
-  if (int rc = match_events(ctx)) return rc;
-  HIPCHK(ctx->m_flag.ensure((size_t)(nq + 1) * sizeof(unsigned)));
-  HIPCHK(ctx->m_off.ensure((size_t)(nq + 1) * sizeof(unsigned)));
-  unsigned* h_n = (unsigned*)ctx->hfeat.p + kFeatPairs;
-  HIPCHK(hipEventRecord(ctx->ev_m[2], ctx->stream));
-  HIPCHK(launch_match_flag(fwd, nq, rev, nt, ratio > 0.0 ? ratio * ratio : 0.0, ctx->m_flag.as<unsigned>(),
-                           ctx->stream));
-  HIPCHK(exclusive_sum(ctx, ctx->m_flag.as<unsigned>(), ctx->m_off.as<unsigned>(), nq + 1));
-  HIPCHK(hipMemcpyAsync(h_n, ctx->m_off.as<unsigned>() + nq, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  *total = *h_n;
-  return SIFT_OK;
-}
-
-// Ends the selection's timing: after the ordered emission of `total` pairs, or
-// (d_pairs == nullptr: a count alone, or too small a buffer) after the count.
-static int select_emit(sift_ctx* ctx, const Match* fwd, int nq, unsigned total, MatchPair* d_pairs) {
-  if (d_pairs)
-    HIPCHK(launch_match_emit(fwd, ctx->m_flag.as<unsigned>(), ctx->m_off.as<unsigned>(), nq, total, d_pairs,
-                             ctx->stream));
-  HIPCHK(hipEventRecord(ctx->ev_m[3], ctx->stream));
-  HIPCHK(hipEventSynchronize(ctx->ev_m[3]));
-  float t = 0;
-  if (hipEventElapsedTime(&t, ctx->ev_m[2], ctx->ev_m[3]) == hipSuccess) ctx->select_ms = t;
-  return SIFT_OK;
-}
-
-int sift_match_select(sift_ctx* ctx, const struct sift_match* d_fwd, size_t n_query, const struct sift_match* d_rev, size_t n_train,
-                      double ratio, sift_match_pair* d_pairs, size_t cap, size_t* n_out) {
-  if (!ctx) return SIFT_E_ARG;
-  if (int rc = select_check(ctx, d_fwd, n_query, n_train, ratio)) return rc;
-  HIPCHK(hipSetDevice(ctx->device));
-  ctx->select_ms = 0;
-  unsigned total = 0;
-  if (n_query)
-    if (int rc = select_count(ctx, reinterpret_cast<const Match*>(d_fwd), (int)n_query,
-                              reinterpret_cast<const Match*>(d_rev), (int)n_train, ratio, &total))
-      return rc;
-  if (n_out) *n_out = total;
-  if (!n_query) return SIFT_OK;
-  if (!d_pairs || cap < total) {
-    if (int rc = select_emit(ctx, nullptr, (int)n_query, total, nullptr)) return rc;
-    return d_pairs ? set_err(ctx, SIFT_E_CAPACITY, "pair buffer too small") : SIFT_OK;
-  }
-  return select_emit(ctx, reinterpret_cast<const Match*>(d_fwd), (int)n_query, total,
-                     reinterpret_cast<MatchPair*>(d_pairs));
-}
-
-int sift_match_select_host(sift_ctx* ctx, const struct sift_match* fwd, size_t n_query, const struct sift_match* rev, size_t n_train,
-                           double ratio, sift_match_pair* pairs, size_t cap, size_t* n_out) {
-  if (!ctx) return SIFT_E_ARG;
-  if (int rc = select_check(ctx, fwd, n_query, n_train, ratio)) return rc;
-  HIPCHK(hipSetDevice(ctx->device));
-  ctx->select_ms = 0;
-  unsigned total = 0;
-  if (n_query) {
-    if (int rc = match_upload(ctx, ctx->m_fwd, fwd, n_query * sizeof(Match))) return rc;
-    if (int rc = match_upload(ctx, ctx->m_rev, rev, n_train * sizeof(Match))) return rc;
-    if (int rc = select_count(ctx, ctx->m_fwd.as<Match>(), (int)n_query,
-                              rev && n_train ? ctx->m_rev.as<Match>() : nullptr, (int)n_train, ratio, &total))
-      return rc;
-  }
-  if (n_out) *n_out = total;
-  if (!n_query) return SIFT_OK;
-  if (!pairs || cap < total) {
-    if (int rc = select_emit(ctx, nullptr, (int)n_query, total, nullptr)) return rc;
-    return pairs ? set_err(ctx, SIFT_E_CAPACITY, "pair buffer too small") : SIFT_OK;
-  }
-  HIPCHK(ctx->m_pairs.ensure(std::max<size_t>(total, 1) * sizeof(MatchPair)));
-  if (int rc = select_emit(ctx, ctx->m_fwd.as<Match>(), (int)n_query, total, ctx->m_pairs.as<MatchPair>())) return rc;
-  if (total) HIPCHK(d2h_staged(ctx, pairs, ctx->m_pairs.p, (size_t)total * sizeof(MatchPair)));
-  return SIFT_OK;
-}
-
-int sift_last_match_timings(sift_ctx* ctx, double* match_ms, double* select_ms) {
-  if (!ctx) return SIFT_E_ARG;
-  if (match_ms) *match_ms = ctx->match_ms;
-  if (select_ms) *select_ms = ctx->select_ms;
-  return SIFT_OK;
-}
-
-// ---- Homography verification (sift_verify.hip) ------------------------------
-static_assert(sizeof(sift_point_pair) == 32 && sizeof(PointPair) == 32 && sizeof(sift_homography) == 80 &&
-                  sizeof(Homography) == 80 && SIFT_RANSAC_MAX_HYPOTHESES == kMaxHypotheses,
-              "verification records and limits of include/sift_hip.h");
-
-static int verify_events(sift_ctx* ctx) {
-  for (auto& e : ctx->ev_v)
-    if (!e) HIPCHK(hipEventCreate(&e));
-  HIPCHK(ctx->hver.ensure(sizeof(Homography) + sizeof(unsigned)));
-  return SIFT_OK;
-}
-
-static int verify_check(sift_ctx* ctx, const void* points, size_t n, size_t K, double thresh) {
-  if (!match_count_ok(n)) return set_err(ctx, SIFT_E_ARG, "too many pairs");
-  if (K > (size_t)kMaxHypotheses) return set_err(ctx, SIFT_E_ARG, "more than SIFT_RANSAC_MAX_HYPOTHESES hypotheses");
-  if (!(std::isfinite(thresh) && thresh > 0.0)) return set_err(ctx, SIFT_E_ARG, "thresh must be finite and > 0");
-  if (n && !points) return set_err(ctx, SIFT_E_ARG, "null pairs");
-  return SIFT_OK;
-}
-
-static double event_ms(hipEvent_t a, hipEvent_t b) {
-  float t = 0;
-  return hipEventElapsedTime(&t, a, b) == hipSuccess ? t : 0.0;
-}
-
-// counts[k] of validated device arrays (K > 0), between the scoring's two events; not waited for.
-static int score_enqueue(sift_ctx* ctx, const PointPair* pts, int n, const double* H, int K, double t2, int* counts) {
-  HIPCHK(hipEventRecord(ctx->ev_v[2], ctx->stream));
-  HIPCHK(hipMemsetAsync(counts, 0, (size_t)K * sizeof(int), ctx->stream));
-  HIPCHK(launch_homography_score(pts, n, H, K, t2, counts, ctx->stream));
-  HIPCHK(hipEventRecord(ctx->ev_v[3], ctx->stream));
-  return SIFT_OK;
-}
-
-static int score_run(sift_ctx* ctx, const PointPair* pts, size_t n, const double* H, size_t K, double thresh,
-                     int* counts) {
-  if (int rc = verify_events(ctx)) return rc;
-  ctx->v_score_ms = 0;
-  if (!K) return SIFT_OK;
-  if (int rc = score_enqueue(ctx, pts, (int)n, H, (int)K, thresh * thresh, counts)) return rc;
-  HIPCHK(hipEventSynchronize(ctx->ev_v[3]));
-  ctx->v_score_ms = event_ms(ctx->ev_v[2], ctx->ev_v[3]);
-  return SIFT_OK;
-}
-
-int sift_homography_score_device(sift_ctx* ctx, const sift_point_pair* d_points, size_t n, const double* d_H, size_t K,
-                                 double thresh, int32_t* d_counts) {
-  if (!ctx) return SIFT_E_ARG;
-  if (int rc = verify_check(ctx, d_points, n, K, thresh)) return rc;
-  if (K && (!d_H || !d_counts)) return set_err(ctx, SIFT_E_ARG, "null matrices or counts");
-  HIPCHK(hipSetDevice(ctx->device));
-  return score_run(ctx, reinterpret_cast<const PointPair*>(d_points), n, d_H, K, thresh, d_counts);
-}
-
-int sift_homography_score(sift_ctx* ctx, const sift_point_pair* points, size_t n, const double* H, size_t K,
-                          double thresh, int32_t* counts) {
-  if (!ctx) return SIFT_E_ARG;
-  if (int rc = verify_check(ctx, points, n, K, thresh)) return rc;
-  if (K && (!H || !counts)) return set_err(ctx, SIFT_E_ARG, "null matrices or counts");
-  HIPCHK(hipSetDevice(ctx->device));
-  if (!K) return score_run(ctx, nullptr, n, nullptr, 0, thresh, nullptr);
-  if (int rc = match_upload(ctx, ctx->v_in_pts, points, n * sizeof(PointPair))) return rc;
-  if (int rc = match_upload(ctx, ctx->v_in_H, H, K * 9 * sizeof(double))) return rc;
-  HIPCHK(ctx->v_in_cnt.ensure(K * sizeof(int)));
-  if (int rc = score_run(ctx, ctx->v_in_pts.as<PointPair>(), n, ctx->v_in_H.as<double>(), K, thresh,
-                         ctx->v_in_cnt.as<int>()))
-    return rc;
-  HIPCHK(d2h_staged(ctx, counts, ctx->v_in_cnt.p, K * sizeof(int)));
-  return SIFT_OK;
-}
-
-// RANSAC over validated device points: the model and the count always, the
-// list into d_inliers when it is given and cap holds it.
-static int ransac_run(sift_ctx* ctx, const PointPair* pts, size_t n, size_t K, uint64_t seed, double thresh,
-                      sift_homography* model, int32_t* d_inliers, size_t cap, size_t* n_inliers) {
-  if (int rc = verify_events(ctx)) return rc;
-  ctx->v_hyp_ms = ctx->v_score_ms = ctx->v_select_ms = 0;
-  ctx->have_ransac = false;
-  ctx->n_hyp = 0;
-  if (n < 4 || K == 0) {  // no hypothesis is formed
-    std::memset(model, 0, sizeof *model);
-    model->hypothesis = -1;
-    if (n_inliers) *n_inliers = 0;
-    ctx->have_ransac = true;
-    return SIFT_OK;
-  }
-  const int ni = (int)n, Ki = (int)K;
-  const double t2 = thresh * thresh;
-  HIPCHK(ctx->v_H.ensure(K * 9 * sizeof(double)));
-  HIPCHK(ctx->v_valid.ensure(K * sizeof(int)));
-  HIPCHK(ctx->v_cnt.ensure(K * sizeof(int)));
-  HIPCHK(ctx->v_model.ensure(sizeof(Homography)));
-  HIPCHK(ctx->v_flag.ensure((n + 1) * sizeof(unsigned)));
-  HIPCHK(ctx->v_off.ensure((n + 1) * sizeof(unsigned)));
-  Homography* h_model = (Homography*)ctx->hver.p;
-  unsigned* h_n = (unsigned*)(h_model + 1);
-  HIPCHK(hipEventRecord(ctx->ev_v[0], ctx->stream));
-  HIPCHK(launch_homography_hypotheses(pts, ni, Ki, seed, ctx->v_H.as<double>(), ctx->v_valid.as<int>(), ctx->stream));
-  HIPCHK(hipEventRecord(ctx->ev_v[1], ctx->stream));
-  if (int rc = score_enqueue(ctx, pts, ni, ctx->v_H.as<double>(), Ki, t2, ctx->v_cnt.as<int>())) return rc;
-  HIPCHK(hipEventRecord(ctx->ev_v[4], ctx->stream));
-  HIPCHK(launch_homography_best(ctx->v_H.as<double>(), ctx->v_valid.as<int>(), ctx->v_cnt.as<int>(), Ki,
-                                ctx->v_model.as<Homography>(), ctx->stream));
-  HIPCHK(launch_inlier_flag(pts, ni, ctx->v_model.as<Homography>(), t2, ctx->v_flag.as<unsigned>(), ctx->stream));
-  HIPCHK(exclusive_sum(ctx, ctx->v_flag.as<unsigned>(), ctx->v_off.as<unsigned>(), ni + 1));
-  HIPCHK(hipMemcpyAsync(h_model, ctx->v_model.p, sizeof(Homography), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipMemcpyAsync(h_n, ctx->v_off.as<unsigned>() + ni, sizeof(unsigned), hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  const unsigned total = *h_n;
-  std::memcpy(model, h_model, sizeof *model);
-  if (n_inliers) *n_inliers = total;
-  const bool fits = cap >= total;
-  if (d_inliers && fits)
-    HIPCHK(launch_inlier_emit(ctx->v_flag.as<unsigned>(), ctx->v_off.as<unsigned>(), ni, total, d_inliers,
-                              ctx->stream));
-  HIPCHK(hipEventRecord(ctx->ev_v[5], ctx->stream));
-  HIPCHK(hipEventSynchronize(ctx->ev_v[5]));
-  ctx->v_hyp_ms = event_ms(ctx->ev_v[0], ctx->ev_v[1]);
-  ctx->v_score_ms = event_ms(ctx->ev_v[2], ctx->ev_v[3]);
-  ctx->v_select_ms = event_ms(ctx->ev_v[4], ctx->ev_v[5]);
-  ctx->n_hyp = K;
-  ctx->have_ransac = true;
-  if (d_inliers && !fits) return set_err(ctx, SIFT_E_CAPACITY, "inlier buffer too small");
-  return SIFT_OK;
-}
-
-int sift_homography_ransac_device(sift_ctx* ctx, const sift_point_pair* d_points, size_t n, size_t K, uint64_t seed,
-                                  double thresh, sift_homography* model, int32_t* d_inliers, size_t cap,
-                                  size_t* n_inliers) {
-  if (!ctx) return SIFT_E_ARG;
-  if (int rc = verify_check(ctx, d_points, n, K, thresh)) return rc;
-  if (!model) return set_err(ctx, SIFT_E_ARG, "null model");
-  HIPCHK(hipSetDevice(ctx->device));
-  return ransac_run(ctx, reinterpret_cast<const PointPair*>(d_points), n, K, seed, thresh, model, d_inliers, cap,
-                    n_inliers);
-}
-
-// ransac_run with the list through ctx->v_inl into host memory.
-static int ransac_to_host(sift_ctx* ctx, const PointPair* pts, size_t n, size_t K, uint64_t seed, double thresh,
-                          sift_homography* model, int32_t* inliers, size_t cap, size_t* n_inliers) {
-  if (inliers) HIPCHK(ctx->v_inl.ensure(std::max<size_t>(n, 1) * sizeof(int32_t)));
-  size_t total = 0;
-  if (int rc = ransac_run(ctx, pts, n, K, seed, thresh, model, inliers ? ctx->v_inl.as<int32_t>() : nullptr, cap,
-                          &total)) {
-    if (rc == SIFT_E_CAPACITY && n_inliers) *n_inliers = total;
-    return rc;
-  }
-  if (n_inliers) *n_inliers = total;
-  if (inliers && total) HIPCHK(d2h_staged(ctx, inliers, ctx->v_inl.p, total * sizeof(int32_t)));
-  return SIFT_OK;
-}
-
-int sift_homography_ransac(sift_ctx* ctx, const sift_point_pair* points, size_t n, size_t K, uint64_t seed,
-                           double thresh, sift_homography* model, int32_t* inliers, size_t cap, size_t* n_inliers) {
-  if (!ctx) return SIFT_E_ARG;
-  if (int rc = verify_check(ctx, points, n, K, thresh)) return rc;
-  if (!model) return set_err(ctx, SIFT_E_ARG, "null model");
-  HIPCHK(hipSetDevice(ctx->device));
-  if (int rc = match_upload(ctx, ctx->v_in_pts, points, n * sizeof(PointPair))) return rc;
-  return ransac_to_host(ctx, ctx->v_in_pts.as<PointPair>(), n, K, seed, thresh, model, inliers, cap, n_inliers);
-}
-
-int sift_copy_homography_hypotheses(sift_ctx* ctx, double* H, int32_t* counts, size_t cap, size_t* n_out) {
-  if (!ctx) return SIFT_E_ARG;
-  if (!ctx->have_ransac) return set_err(ctx, SIFT_E_STATE, "no RANSAC: run sift_homography_ransac first");
-  const size_t K = ctx->n_hyp;
-  if (n_out) *n_out = K;
-  if ((!H && !counts) || !K) return SIFT_OK;
-  if (cap < K) return set_err(ctx, SIFT_E_CAPACITY, "hypothesis buffer too small");
-  HIPCHK(hipSetDevice(ctx->device));
-  if (H) HIPCHK(d2h_staged(ctx, H, ctx->v_H.p, K * 9 * sizeof(double)));
-  if (counts) HIPCHK(d2h_staged(ctx, counts, ctx->v_cnt.p, K * sizeof(int)));
-  return SIFT_OK;
-}
-
-// Both sides have the orientation records the pairs index, on one device.
-static int pair_points_check(sift_ctx* ctx, sift_ctx* train_ctx) {
-  for (sift_ctx* c : {ctx, train_ctx})
-    if (c->detect_pending || c->begin_pending || !c->have_kp || !c->have_ori)
-      return set_err(ctx, SIFT_E_STATE, "no orientations: run sift_orient on both contexts first");
-  if (ctx->device != train_ctx->device) return set_err(ctx, SIFT_E_ARG, "contexts on different devices");
-  return SIFT_OK;
-}
-
-static int pair_points_enqueue(sift_ctx* ctx, sift_ctx* train_ctx, const MatchPair* d_pairs, size_t n,
-                               PointPair* d_points) {
-  HIPCHK(launch_pair_points(d_pairs, (int)n, ctx->ori.as<Orientation>(), (int)ctx->n_ori, ctx->kp.as<Keypoint>(),
-                            (int)ctx->n_kp, train_ctx->ori.as<Orientation>(), (int)train_ctx->n_ori,
-                            train_ctx->kp.as<Keypoint>(), (int)train_ctx->n_kp, d_points, ctx->stream));
-  return SIFT_OK;
-}
-
-int sift_pair_points_device(sift_ctx* ctx, sift_ctx* train_ctx, const sift_match_pair* d_pairs, size_t n,
-                            sift_point_pair* d_points) {
-  if (!ctx || !train_ctx) return SIFT_E_ARG;
-  if (!match_count_ok(n)) return set_err(ctx, SIFT_E_ARG, "too many pairs");
-  if (n && (!d_pairs || !d_points)) return set_err(ctx, SIFT_E_ARG, "null pairs or points");
-  if (int rc = pair_points_check(ctx, train_ctx)) return rc;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (int rc = pair_points_enqueue(ctx, train_ctx, reinterpret_cast<const MatchPair*>(d_pairs), n,
-                                   reinterpret_cast<PointPair*>(d_points)))
-    return rc;
-  HIPCHK(hipStreamSynchronize(ctx->stream));
-  return SIFT_OK;
-}
-
-int sift_verify_features(sift_ctx* ctx, sift_ctx* train_ctx, const sift_match_pair* pairs, size_t n, size_t K,
-                         uint64_t seed, double thresh, sift_homography* model, int32_t* inliers, size_t cap,
-                         size_t* n_inliers) {
-  if (!ctx || !train_ctx) return SIFT_E_ARG;
-  if (int rc = verify_check(ctx, pairs, n, K, thresh)) return rc;
-  if (!model) return set_err(ctx, SIFT_E_ARG, "null model");
-  if (int rc = pair_points_check(ctx, train_ctx)) return rc;
-  HIPCHK(hipSetDevice(ctx->device));
-  if (int rc = match_upload(ctx, ctx->v_pairs, pairs, n * sizeof(MatchPair))) return rc;
-  HIPCHK(ctx->v_pts.ensure(std::max<size_t>(n, 1) * sizeof(PointPair)));
-  if (int rc = pair_points_enqueue(ctx, train_ctx, ctx->v_pairs.as<MatchPair>(), n, ctx->v_pts.as<PointPair>()))
-    return rc;
-  return ransac_to_host(ctx, ctx->v_pts.as<PointPair>(), n, K, seed, thresh, model, inliers, cap, n_inliers);
-}
-
-int sift_last_verify_timings(sift_ctx* ctx, double* hypotheses_ms, double* score_ms, double* select_ms) {
-  if (!ctx) return SIFT_E_ARG;
-  if (hypotheses_ms) *hypotheses_ms = ctx->v_hyp_ms;
-  if (score_ms) *score_ms = ctx->v_score_ms;
-  if (select_ms) *select_ms = ctx->v_select_ms;
-  return SIFT_OK;
 }
 
 int sift_set_flags(sift_ctx* ctx, int flags) {

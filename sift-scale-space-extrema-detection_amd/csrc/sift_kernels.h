@@ -303,8 +303,8 @@ hipError_t launch_kp_soa(const Keypoint* kp, int n, int32_t* ints, double* reals
 hipError_t launch_decode_origins(const Pyramid& P, const unsigned* keys, int n, int32_t* out, hipStream_t st);
 
 // Orientation assignment and descriptors (sift_feature.hip).  The constants
-// are the SIFT_ORI_* / SIFT_DESC_* of include/sift_hip.h (sift_api.hip
-// asserts the match).
+// are the SIFT_ORI_* / SIFT_DESC_* of include/sift_hip.h
+// (sift_api_feature.hip asserts the match).
 constexpr int kOriBins = 36, kOriSmooth = 6, kOriMaxPeaks = 18;
 constexpr double kOriLambda = 1.5, kOriPeakRatio = 0.8;
 constexpr int kDescOri = 8, kDescBytes = 128;

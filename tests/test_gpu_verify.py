@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import match_ref as mr
 import ransac_ref as rr
 import sift_amd
 from sift_amd.synth import blob_image
@@ -323,3 +324,74 @@ def test_end_to_end(gpu_ctx):
             with pytest.raises(sift_amd.SiftError) as e:
                 gpu_ctx.verify_features(fresh, pairs, K, seed, thresh)
             assert e.value.code == sift_amd.SIFT_E_STATE
+
+
+# ---- the mechanisms the feature, match and verify stages share -------------------------
+def test_selection_and_inliers_at_the_scan_edges(gpu_ctx):
+    """Selection and RANSAC at the 256-item edges of the flag grids and of the
+    n + 1 scan.  Every second query is a train row, so that the ratio test accepts
+    some records and rejects the others; every planted pair is an inlier, so the
+    total is n.  Sizes descending, then ascending, on the one context: the pinned
+    count word and the grown flag / offset buffers are reused by a smaller list."""
+    cases = {}
+    for nq, n in ((1, 4), (255, 255), (256, 256), (257, 257)):
+        query = np.random.default_rng(400 + nq).integers(0, 256, (nq, 128), dtype=np.uint8)
+        train = np.random.default_rng(500 + nq).integers(0, 256, (300, 128), dtype=np.uint8)
+        k = (nq + 1) // 2
+        train[:k] = query[::2]
+        fwd = gpu_ctx.match(query, train)
+        want = {r: mr.select_ref(fwd, None, r) for r in (0.0, 0.8)}
+        assert len(want[0.0]) == nq and len(want[0.8]) == k
+        pts, _, _ = rr.planted(n, 1.0, 0.0, 600 + n)
+        ref = rr.ransac_homography(pts, 64, 600 + n, 3.0)
+        assert ref[1] >= 0 and len(ref[2]) == n
+        cases[nq] = (fwd, want, pts, ref, n)
+    for nq in (257, 256, 255, 1, 255, 256, 257):
+        fwd, want, pts, ref, n = cases[nq]
+        for ratio in (0.0, 0.8):
+            got = gpu_ctx.select_matches(fwd, None, ratio)
+            assert got.dtype == want[ratio].dtype and got.tobytes() == want[ratio].tobytes(), (nq, ratio)
+        assert_result(gpu_ctx.ransac_homography(pts, 64, 600 + n, 3.0), ref)
+
+
+def test_stages_keep_their_own_state(gpu_ctx):
+    """Feature, match and verify results and timings on one context survive the
+    other stages' calls (which share one pinned read-back and one scan scratch)."""
+    L, h = sift_amd.lib(), gpu_ctx._h
+    p = sift_amd.make_params(3, 4)
+    with sift_amd.Context(0) as other:
+        for ctx, seed in ((gpu_ctx, 1), (other, 2)):
+            ctx.detect(blob_image(256, 256, seed=seed), p)
+            ctx.orient()
+            ctx.describe()
+        ori, (desc, ok) = gpu_ctx.orient(), gpu_ctx.describe()
+        fwd, rev = gpu_ctx.match_features(other), other.match_features(gpu_ctx)
+        pairs = gpu_ctx.select_matches(fwd, rev, 0.0)
+        assert len(ori) > 100 and ok.sum() > 100 and len(pairs) >= 4
+        model = gpu_ctx.verify_features(other, pairs, 128, 5, 3.0)
+        assert len(gpu_ctx.homography_hypotheses()[1]) == 128
+        ft, mt, vt = gpu_ctx.feature_timings(), gpu_ctx.match_timings(), gpu_ctx.verify_timings()
+        assert min(ft.values()) > 0 and min(mt.values()) > 0 and min(vt.values()) > 0
+
+        n = ctypes.c_size_t(99)                                               # a count alone
+        f = fwd.ctypes.data_as(ctypes.c_void_p)
+        assert L.sift_match_select_host(h, f, len(fwd), None, len(rev), 0.0, None, 0, ctypes.byref(n)) == 0
+        assert n.value == len(mr.select_ref(fwd, None, 0.0)) >= len(pairs)
+        assert gpu_ctx.match_timings()["match_ms"] == mt["match_ms"]
+        assert gpu_ctx.feature_timings() == ft and gpu_ctx.verify_timings() == vt
+
+        pts, _, _ = rr.planted(4, 1.0, 0.0, 11)
+        assert_result(gpu_ctx.ransac_homography(pts, 16, 0, 3.0), rr.ransac_homography(pts, 16, 0, 3.0))
+        assert gpu_ctx.match_timings()["match_ms"] == mt["match_ms"]
+        assert len(gpu_ctx.homography_hypotheses()[1]) == 16                  # that run's K, not the earlier one's
+        vt4 = gpu_ctx.verify_timings()
+
+        assert gpu_ctx.orient().tobytes() == ori.tobytes()                    # served from the context
+        assert gpu_ctx.feature_timings() == ft
+        desc2, ok2 = gpu_ctx.describe()
+        assert desc2.tobytes() == desc.tobytes() and ok2.tobytes() == ok.tobytes()
+        assert gpu_ctx.match_features(other).tobytes() == fwd.tobytes()
+        assert gpu_ctx.verify_timings() == vt4
+        again = gpu_ctx.verify_features(other, pairs, 128, 5, 3.0)
+        for a, b in zip(again, model):
+            assert np.asarray(a).tobytes() == np.asarray(b).tobytes()
