@@ -639,9 +639,8 @@ int sift_last_match_timings(struct sift_ctx *ctx, double *match_ms, double *sele
  * Limits: K <= SIFT_RANSAC_MAX_HYPOTHESES, n < 2^31 - 1, thresh finite and > 0,
  * pointers non-NULL where a count is non-zero: else SIFT_E_ARG, nothing written.
  *
- * Not here: a least-squares refit over the inliers (it needs an ordered fp64
- * reduction of its own and builds on the inlier list returned), symmetric
- * transfer error, adaptive termination, fundamental or essential matrices. */
+ * Not here: symmetric transfer error, adaptive termination, fundamental or
+ * essential matrices.  The least-squares refit over the inliers follows below. */
 #define SIFT_RANSAC_MAX_HYPOTHESES 65536
 
 /* A point of the query image and its putative partner in the train image, in
@@ -701,6 +700,119 @@ int sift_verify_features(struct sift_ctx *ctx, struct sift_ctx *train_ctx, const
  * scoring (sift_homography_score* sets this one alone), and the selection (best
  * hypothesis, flags, scan, count read-back, and the emission when written). */
 int sift_last_verify_timings(struct sift_ctx *ctx, double *hypotheses_ms, double *score_ms, double *select_ms);
+
+/* ---- Least-squares refit of the RANSAC inliers -------------------------------
+ *
+ * The best RANSAC model interpolates four noisy pairs; the refit fits a
+ * homography to all of its inliers, rescores, and repeats while the inlier
+ * count grows.  Like the stage above it uses only + - * /, comparisons and
+ * negation in fp64 with no contraction, no sqrt and no library function, and it
+ * is bit-identical from run to run: the one floating-point sum over a
+ * data-dependent list is taken in a fixed tree (step 3).  These entry points
+ * are detected by symbol; SIFT_ABI_VERSION stays 9.
+ *
+ * Fit of a list I of m >= 4 pair indices (each < n; repeats are legal).  The
+ * list order is the summation order; the refit passes ascending indices.
+ *  1. Box normalisation, per image side.  Over the listed pairs lo_x, hi_x,
+ *     lo_y, hi_y are the smallest and largest query coordinate that is not a
+ *     NaN (a NaN when there is none); a bound that is a zero is taken as +0
+ *     (lo = lo + 0.0).  Then
+ *       cx = (lo_x + hi_x) * 0.5, cy = (lo_y + hi_y) * 0.5,
+ *       w = hi_x - lo_x, g = hi_y - lo_y, dq = (g > w ? g : w) * 0.5.
+ *     The train side gives cX, cY, dt in the same way.  The fit is invalid unless
+ *     dq > 0 && dt > 0 and both are finite.  Normalised coordinates are
+ *     x' = (x - cx) / dq, y' = (y - cy) / dq, X' = (X - cX) / dt, Y' = (Y - cY) / dt.
+ *     Minimum and maximum are exact and do not depend on the order: this is why
+ *     the normalisation uses the box and not a mean distance.
+ *  2. Normal equations.  With the normalised point (written x, y, X, Y), the
+ *     rows of RANSAC step 2:
+ *       a = [x, y, 1, 0, 0, 0, -(X*x), -(X*y) | X],
+ *       b = [0, 0, 0, x, y, 1, -(Y*x), -(Y*y) | Y].
+ *     For 0 <= j <= k <= 8, j <= 7 (44 sums, in this row-major order) the term of
+ *     pair i is t_i = a_j*a_k + b_j*b_k: both products rounded, then added, the
+ *     zeros and ones multiplied like every other entry.  N[j][k] = N[k][j] = the
+ *     sum of t_i, g[j] = N[j][8].
+ *  3. Summation order: a fixed tree that depends on m alone.  The terms, in list
+ *     order, are split into chunks of 64, the last one padded with +0.0.  A
+ *     chunk's sum is the halving tree: for s = 32, 16, 8, 4, 2, 1: p[i] = p[i] +
+ *     p[i + s] for i < s; the sum is p[0].  The ceil(m / 64) chunk sums are
+ *     reduced by the same rule, and so on until one value is left (a single
+ *     chunk sum is the result as it is).
+ *  4. [N | g] is solved for h'[0..7] by exactly the elimination and back
+ *     substitution of RANSAC step 3, pivot rule included; a zero or non-finite
+ *     pivot or a non-finite h' makes the fit invalid.
+ *  5. Denormalisation.  With Hn = [h'0 .. h'7, 1] row-major, for r = 0, 1, 2:
+ *       G[r][0] = Hn[r][0] / dq, G[r][1] = Hn[r][1] / dq,
+ *       G[r][2] = Hn[r][2] - (Hn[r][0]*cx + Hn[r][1]*cy) / dq;
+ *     for c = 0, 1, 2:
+ *       F[0][c] = dt*G[0][c] + cX*G[2][c], F[1][c] = dt*G[1][c] + cY*G[2][c],
+ *       F[2][c] = G[2][c];
+ *     h = F / F[2][2] element by element, so h[8] is exactly 1.  The fit is
+ *     invalid if F[2][2] is zero or not finite, or if any h is not finite.
+ *  An invalid fit gives nine zeros.  A list of fewer than four entries is an
+ *  invalid fit that forms no box and no sums.
+ *
+ * Refit of a starting model H0 (any nine doubles, h[8] as given) over n pairs at
+ * `thresh` with at most R = max_rounds rounds.  I_0 = the inliers of H0 by the
+ * inlier rule above, ascending, c_0 = |I_0|.  Round r = 1 .. R:
+ *   if c_{r-1} < 4, stop.  Fit I_{r-1}; if the fit is invalid, stop.  Apply the
+ *   inlier rule to all n pairs: I_r, c_r.  If c_r < c_{r-1}, discard the round
+ *   and stop.  Otherwise accept it, and stop after accepting if c_r == c_{r-1}
+ *   or r == R.
+ * The result is the last accepted matrix, its count, its ascending inlier list
+ * and the number of accepted rounds; with none accepted it is H0 unchanged with
+ * I_0.  The host compares integers only.  R == 0, n == 0 and a "none" model (all
+ * zeros, so no inliers) are valid calls.
+ *
+ * Limits: 0 <= R <= SIFT_REFIT_MAX_ROUNDS, n < 2^31 - 1 (and m < 2^31 - 1),
+ * thresh finite and > 0, pointers non-NULL where a count is non-zero, every
+ * entry of a host list < n: else SIFT_E_ARG, nothing written.  A device list
+ * cannot be checked on the host: an entry outside [0, n) is not read through,
+ * and makes the fit invalid. */
+#define SIFT_REFIT_MAX_ROUNDS 16
+
+/* One fit of the list d_index[0 .. m) over n device point pairs; d_index == NULL
+ * means the list 0 .. n-1 (m is not read).  h (host memory, nine doubles) and
+ * *valid (1 / 0; may be NULL) receive the result; m < 4 is an invalid fit and
+ * SIFT_OK.  Complete on return. */
+int sift_homography_fit_device(struct sift_ctx *ctx, const sift_point_pair *d_points, size_t n, const int32_t *d_index,
+                               size_t m, double *h, int *valid);
+/* The same with host points and a host list, through the context's own device buffers. */
+int sift_homography_fit(struct sift_ctx *ctx, const sift_point_pair *points, size_t n, const int32_t *index, size_t m,
+                        double *h, int *valid);
+
+/* box = cx, cy, dq, cX, cY, dt and the 44 sums (step 2's order) of the last fit
+ * on ctx -- by the two calls above, or the last round a refit tried -- valid or
+ * not; either array may be NULL.  SIFT_E_STATE without a fit, or after one of
+ * fewer than four entries.  The fit keeps its own state: a RANSAC or a scoring
+ * on ctx leaves these values as they are. */
+int sift_copy_homography_fit_sums(struct sift_ctx *ctx, double *box, double *sums);
+
+/* The refit of *start over n device point pairs.  *refined (host memory; it may
+ * be start) receives the matrix and the count, with `hypothesis` copied from
+ * *start; *rounds the accepted rounds; *n_inliers the count; d_inliers (device
+ * memory, cap indices) the inlier list, or NULL to only count.
+ * SIFT_E_CAPACITY when cap < *n_inliers: everything but the list is set.
+ * rounds and n_inliers may be NULL.  Complete on return; the RANSAC state of ctx
+ * (sift_copy_homography_hypotheses) is left as it is. */
+int sift_homography_refit_device(struct sift_ctx *ctx, const sift_point_pair *d_points, size_t n,
+                                 const sift_homography *start, double thresh, int max_rounds, sift_homography *refined,
+                                 int32_t *rounds, int32_t *d_inliers, size_t cap, size_t *n_inliers);
+/* The same with host points and a host inlier list. */
+int sift_homography_refit(struct sift_ctx *ctx, const sift_point_pair *points, size_t n, const sift_homography *start,
+                          double thresh, int max_rounds, sift_homography *refined, int32_t *rounds, int32_t *inliers,
+                          size_t cap, size_t *n_inliers);
+
+/* sift_verify_features followed by the refit of its model, on the points already
+ * gathered on the device: host pairs in, host results out. */
+int sift_verify_features_refit(struct sift_ctx *ctx, struct sift_ctx *train_ctx, const sift_match_pair *pairs, size_t n,
+                               size_t K, uint64_t seed, double thresh, int max_rounds, sift_homography *model,
+                               int32_t *rounds, int32_t *inliers, size_t cap, size_t *n_inliers);
+
+/* Device time of the last refit, milliseconds, summed over the rounds it tried
+ * (a discarded one included): the fits (box, sums, solve) and the rescoring
+ * (flags, scan, read-back, emission).  Both 0 when no round was tried. */
+int sift_last_refit_timings(struct sift_ctx *ctx, double *fit_ms, double *rescore_ms);
 
 /* Wait for all work queued on ctx's stream. */
 int sift_synchronize(struct sift_ctx *ctx);

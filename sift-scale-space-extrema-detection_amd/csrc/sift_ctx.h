@@ -1,5 +1,5 @@
 // The context behind the C ABI and what its host files share (sift_api.hip,
-// sift_api_feature / _match / _verify.hip).  No kernel file includes this.
+// sift_api_feature / _match / _verify / _refit.hip).  No kernel file includes this.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -94,9 +94,21 @@ struct VerifyState {
   double hyp_ms = 0, score_ms = 0, select_ms = 0;
 };
 
+// Least-squares fit and refit of the inliers (sift_api_refit.hip).
+struct RefitState {
+  DBuf keys, parts_a, parts_b, rec;            // one fit: box keys, the tree's levels (ping-pong), its FitRecord
+  DBuf start, flag, off;                       // the rounds: the start's model record, inlier flags, their scan
+  DBuf list[2];                                // ... the accepted inlier list (cur) and the round's candidate
+  DBuf in_pts, in_idx;                         // host-form inputs (sift_homography_fit, sift_homography_refit)
+  int cur = 0; size_t n_list = 0;              // the last refit's list: list[cur][0 .. n_list)
+  bool have_fit = false;                       // rec holds a fit (box and sums included)
+  EventSet<3> ev;                              // a round: before the fit [0], after it [1], after the rescoring [2]
+  double fit_ms = 0, rescore_ms = 0;
+};
+
 // Pinned read-backs of those stages (sift_ctx::hscratch): one of each serves them all, since every user synchronises.
 struct StageScratch {
-  Homography model;  // the RANSAC's
+  Homography model;  // the RANSAC's; a fit's
   unsigned word;     // a count
 };
 
@@ -191,6 +203,7 @@ struct sift_ctx {
   sift::FeatState feat;
   sift::MatchState match;
   sift::VerifyState verify;
+  sift::RefitState refit;
   HBuf hscratch;                               // pinned: one sift::StageScratch (sift_ctx_create)
   DBuf counters, temp;
   DBuf rgba, alpha, display, mm_parts;         // image products (sift_image.hip)

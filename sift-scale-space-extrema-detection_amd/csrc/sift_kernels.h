@@ -404,6 +404,47 @@ __host__ __device__ inline bool homography_inlier(double h0, double h1, double h
   const bool front = w > 0.0, near = (du * du + dv * dv) < t2 * (w * w);
   return front & near;  // both evaluated: no branch around the second in the score loop
 }
+// Step 3 of the RANSAC definition, the one statement of it: the hypothesis
+// kernel and the refit's solve kernel call it.  Entry (r, c) of the 8 x 9
+// system [A | b] is a[(r * 9 + c) * kStride] (LDS: the pivot row is a runtime
+// index, which in registers would mean scratch); h receives the eight
+// unknowns.  False for a zero or non-finite pivot or a non-finite h; the
+// elimination is carried to the end either way.
+template <int kStride>
+__device__ __forceinline__ bool homography_solve(double* a, double (&h)[8]) {
+#pragma clang fp contract(off)
+#define A_(r, c) a[((r) * 9 + (c)) * kStride]
+  bool ok = true;
+  for (int c = 0; c < 8; ++c) {
+    int p = c;
+    double best = __builtin_fabs(A_(c, c));
+    for (int r = c + 1; r < 8; ++r) {
+      const double m = __builtin_fabs(A_(r, c));
+      if (m > best) best = m, p = r;
+    }
+    if (!(best > 0.0 && best < __builtin_huge_val())) ok = false;  // zero, infinite or NaN
+    for (int j = c; j < 9; ++j) {                                   // p == c swaps a row with itself
+      const double t = A_(p, j);
+      A_(p, j) = A_(c, j);
+      A_(c, j) = t;
+    }
+    const double piv = A_(c, c);
+    for (int r = c + 1; r < 8; ++r) {
+      const double f = A_(r, c) / piv;
+      for (int j = c + 1; j < 9; ++j) A_(r, j) = A_(r, j) - f * A_(c, j);
+    }
+  }
+#pragma unroll
+  for (int c = 7; c >= 0; --c) {
+    double t = A_(c, 8);
+#pragma unroll
+    for (int j = c + 1; j < 8; ++j) t = t - A_(c, j) * h[j];
+    h[c] = t / A_(c, c);
+    if (!(__builtin_fabs(h[c]) < __builtin_huge_val())) ok = false;
+  }
+#undef A_
+  return ok;
+}
 // points[i] = (abs_x, abs_y) of the query and of the train keypoint behind pair
 // i's orientation records; four NaNs when an index is outside its list.
 hipError_t launch_pair_points(const MatchPair* pairs, int n, const Orientation* q_ori, int nq_ori, const Keypoint* q_kp,
@@ -424,6 +465,29 @@ hipError_t launch_inlier_flag(const PointPair* points, int n, const Homography* 
 // off = the exclusive scan of flag: the inlier indices in ascending order (cap slots).
 hipError_t launch_inlier_emit(const unsigned* flag, const unsigned* off, int n, unsigned cap, int32_t* out,
                               hipStream_t st);
+
+// Least-squares homography fit of a list of pairs (sift_refit.hip; the
+// definition is in include/sift_hip.h).
+constexpr int kFitSums = 44;    // the upper triangle of the 8 x 8 normal matrix with column 8, row-major
+constexpr int kFitChunk = 64;   // terms per leaf of the summation tree: one wave
+constexpr int kFitKeys = 9;     // box bounds as ordered integer keys (k_fit_box), and the list's ok word
+constexpr int kMaxRefitRounds = 16;
+// What one fit leaves on the device: the model first (hypothesis 0 for a valid
+// fit, -1 with nine zeros for an invalid one, so that k_inlier_flag of an
+// invalid fit flags nothing), then cx, cy, dq, cX, cY, dt and the 44 sums.
+struct FitRecord {
+  Homography model;
+  double box[6];
+  double sums[kFitSums];
+};
+// Chunk sums the first level of the tree writes for a list of m entries.
+inline long long fit_chunks(long long m) { return (m + kFitChunk - 1) / kFitChunk; }
+// One fit of index[0 .. m) (nullptr: 0 .. m-1, m == n) over n pairs, m >= 4:
+// box, sums, the tree's levels and the solve, all enqueued on st.  keys:
+// kFitKeys words; parts_a / parts_b: fit_chunks(m) * 44 and
+// fit_chunks(fit_chunks(m)) * 44 doubles.
+hipError_t launch_homography_fit(const PointPair* points, int n, const int32_t* index, int m, unsigned long long* keys,
+                                 double* parts_a, double* parts_b, FitRecord* rec, hipStream_t st);
 
 // Image products either side of the path (sift_image.hip).
 // gray/alpha rows are dense (w floats); alpha may be nullptr.

@@ -96,36 +96,9 @@ __global__ void __launch_bounds__(kHypLanes) k_homography_hypotheses(const Point
     srt[i] = v;
   }
 
-  bool ok = true;
-  for (int c = 0; c < 8; ++c) {
-    int p = c;
-    double best = fabs(A_(c, c));
-    for (int r = c + 1; r < 8; ++r) {
-      const double m = fabs(A_(r, c));
-      if (m > best) best = m, p = r;
-    }
-    if (!(best > 0.0 && best < HUGE_VAL)) ok = false;  // zero, infinite or NaN
-    for (int j = c; j < 9; ++j) {                     // p == c swaps a row with itself
-      const double t = A_(p, j);
-      A_(p, j) = A_(c, j);
-      A_(c, j) = t;
-    }
-    const double piv = A_(c, c);
-    for (int r = c + 1; r < 8; ++r) {
-      const double f = A_(r, c) / piv;
-      for (int j = c + 1; j < 9; ++j) A_(r, j) = A_(r, j) - f * A_(c, j);
-    }
-  }
-  double h[8];
-#pragma unroll
-  for (int c = 7; c >= 0; --c) {
-    double t = A_(c, 8);
-#pragma unroll
-    for (int j = c + 1; j < 8; ++j) t = t - A_(c, j) * h[j];
-    h[c] = t / A_(c, c);
-    if (!(fabs(h[c]) < HUGE_VAL)) ok = false;
-  }
 #undef A_
+  double h[8];
+  const bool ok = homography_solve<kHypLanes>(&a[0][lane], h);
 #pragma unroll
   for (int j = 0; j < 8; ++j) H[(size_t)k * 9 + j] = ok ? h[j] : 0.0;
   H[(size_t)k * 9 + 8] = ok ? 1.0 : 0.0;

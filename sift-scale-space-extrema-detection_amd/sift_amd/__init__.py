@@ -66,6 +66,9 @@ ABI_SYMBOLS = (
     "sift_pair_points_device", "sift_homography_ransac_device", "sift_homography_ransac",
     "sift_homography_score", "sift_homography_score_device", "sift_copy_homography_hypotheses",
     "sift_verify_features", "sift_last_verify_timings",
+    "sift_homography_fit_device", "sift_homography_fit", "sift_copy_homography_fit_sums",
+    "sift_homography_refit_device", "sift_homography_refit", "sift_verify_features_refit",
+    "sift_last_refit_timings",
 )
 
 
@@ -120,6 +123,7 @@ PAIR_DTYPE = np.dtype([("query", "<i4"), ("train", "<i4"), ("d2", "<i4"), ("d2_s
 MATCH_NONE_D2 = 2**31 - 1
 POINT_PAIR_DTYPE = np.dtype([("qx", "<f8"), ("qy", "<f8"), ("tx", "<f8"), ("ty", "<f8")])
 RANSAC_MAX_HYPOTHESES = 65536
+REFIT_MAX_ROUNDS = 16
 
 
 class Homography(ctypes.Structure):
@@ -238,6 +242,16 @@ def lib():
         "sift_verify_features": (ctypes.c_int, [vp, vp, vp, sz, sz, ctypes.c_uint64, ctypes.c_double, hp, vp, sz,
                                                 szp]),
         "sift_last_verify_timings": (ctypes.c_int, [vp, dp, dp, dp]),
+        "sift_homography_fit_device": (ctypes.c_int, [vp, vp, sz, vp, sz, dp, ip]),
+        "sift_homography_fit": (ctypes.c_int, [vp, vp, sz, vp, sz, dp, ip]),
+        "sift_copy_homography_fit_sums": (ctypes.c_int, [vp, dp, dp]),
+        "sift_homography_refit_device": (ctypes.c_int, [vp, vp, sz, hp, ctypes.c_double, ctypes.c_int, hp,
+                                                        ctypes.POINTER(ctypes.c_int32), vp, sz, szp]),
+        "sift_homography_refit": (ctypes.c_int, [vp, vp, sz, hp, ctypes.c_double, ctypes.c_int, hp,
+                                                 ctypes.POINTER(ctypes.c_int32), vp, sz, szp]),
+        "sift_verify_features_refit": (ctypes.c_int, [vp, vp, vp, sz, sz, ctypes.c_uint64, ctypes.c_double,
+                                                      ctypes.c_int, hp, ctypes.POINTER(ctypes.c_int32), vp, sz, szp]),
+        "sift_last_refit_timings": (ctypes.c_int, [vp, dp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -914,6 +928,69 @@ class Context:
         self._check(self._L.sift_last_verify_timings(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
                     "sift_last_verify_timings")
         return dict(hypotheses_ms=a.value, score_ms=b.value, select_ms=c.value)
+
+    # -- least-squares refit of the inliers -------------------------------------
+    def fit_homography(self, points, index=None):
+        """The least-squares homography of the listed pairs (int32 indices into
+        POINT_PAIR_DTYPE points, in summation order; None: all of them)
+        (sift_homography_fit): (H float64 [3, 3], valid)."""
+        p = self._points(points)
+        idx = None if index is None else np.ascontiguousarray(index, dtype=np.int32)
+        h, ok = np.zeros(9, dtype=np.float64), ctypes.c_int()
+        dp = ctypes.POINTER(ctypes.c_double)
+        self._check(self._L.sift_homography_fit(self._h, self._ptr(p), p.shape[0], self._ptr(idx),
+                                                0 if idx is None else idx.shape[0], h.ctypes.data_as(dp),
+                                                ctypes.byref(ok)), "sift_homography_fit")
+        return h.reshape(3, 3), bool(ok.value)
+
+    def homography_fit_sums(self):
+        """The last fit's (box float64 [6] = cx, cy, dq, cX, cY, dt; sums float64
+        [44], the upper triangle of [N | g] row-major) (sift_copy_homography_fit_sums)."""
+        box, sums = np.zeros(6, dtype=np.float64), np.zeros(44, dtype=np.float64)
+        dp = ctypes.POINTER(ctypes.c_double)
+        self._check(self._L.sift_copy_homography_fit_sums(self._h, box.ctypes.data_as(dp), sums.ctypes.data_as(dp)),
+                    "sift_copy_homography_fit_sums")
+        return box, sums
+
+    @staticmethod
+    def _start(H, hypothesis=0):
+        h = np.ascontiguousarray(H, dtype=np.float64).reshape(9)
+        return Homography((ctypes.c_double * 9)(*h), int(hypothesis), 0)
+
+    def refit_homography(self, points, H, thresh=3.0, rounds=4):
+        """Refit of the model H [3, 3] over POINT_PAIR_DTYPE points: fit its
+        inliers, rescore, repeat while the count grows, at most `rounds` times
+        (sift_homography_refit): (H float64 [3, 3], accepted rounds, inlier
+        indices int32 ascending)."""
+        p = self._points(points)
+        m, n, r = Homography(), ctypes.c_size_t(), ctypes.c_int32()
+        inl = np.zeros(max(p.shape[0], 1), dtype=np.int32)
+        self._check(self._L.sift_homography_refit(self._h, self._ptr(p), p.shape[0], ctypes.byref(self._start(H)),
+                                                  float(thresh), int(rounds), ctypes.byref(m), ctypes.byref(r),
+                                                  self._ptr(inl), inl.shape[0], ctypes.byref(n)),
+                    "sift_homography_refit")
+        return np.array(m.h, dtype=np.float64).reshape(3, 3), int(r.value), inl[:n.value]
+
+    def verify_features_refit(self, train_ctx, pairs, hypotheses=1024, seed=0, thresh=3.0, rounds=4):
+        """verify_features followed by the refit of its model, on the points
+        already on the device (sift_verify_features_refit): (H float64 [3, 3],
+        index of the RANSAC's best hypothesis or -1, accepted rounds, inlier
+        indices int32 ascending)."""
+        pr = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+        m, n, r = Homography(), ctypes.c_size_t(), ctypes.c_int32()
+        inl = np.zeros(max(pr.shape[0], 1), dtype=np.int32)
+        self._check(self._L.sift_verify_features_refit(self._h, train_ctx._h, self._ptr(pr), pr.shape[0],
+                                                       int(hypotheses), int(seed), float(thresh), int(rounds),
+                                                       ctypes.byref(m), ctypes.byref(r), self._ptr(inl), inl.shape[0],
+                                                       ctypes.byref(n)), "sift_verify_features_refit")
+        return np.array(m.h, dtype=np.float64).reshape(3, 3), int(m.hypothesis), int(r.value), inl[:n.value]
+
+    def refit_timings(self):
+        """Device ms of the last refit, summed over its rounds: the fits and the rescoring."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        self._check(self._L.sift_last_refit_timings(self._h, ctypes.byref(a), ctypes.byref(b)),
+                    "sift_last_refit_timings")
+        return dict(fit_ms=a.value, rescore_ms=b.value)
 
     def stream(self):
         return self._L.sift_stream(self._h)

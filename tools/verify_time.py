@@ -20,8 +20,16 @@ none of them fused: the definition forbids contraction -- as a fraction of the
 multiply-add as two, so half of it is this kernel's ceiling), and how far the
 torch arm's counts are from the kernel's (its product may round differently).
 One run on a shared machine: compare the two arms with each other, not with
-another day's figures."""
+another day's figures.
+
+Every step also refits the RANSAC model on the same device points
+(sift_homography_refit_device, --refit-rounds) and, alternating with it, times
+a torch statement of one fit: the same box-normalised 2m x 8 system over the
+refit's inlier list, solved by fp64 torch.linalg.lstsq on the device.  The
+medians of the refit's fit and rescoring times, the rounds it took and the
+torch times go to --refit-out with this run's score time beside them."""
 import argparse
+import ctypes
 import json
 import os
 import statistics
@@ -47,6 +55,29 @@ def torch_score(torch, Hm, hom, X, Y, t2, chunk):
     return torch.cat(out)
 
 
+def torch_system(torch, xy, inl, box):
+    """The fit's normalised system (A [2m, 8], b [2m, 1]) of the listed rows of xy [M, 4]."""
+    cx, cy, dq, cX, cY, dt = (float(v) for v in box)
+    q = xy[inl]
+    x, y, X, Y = (q[:, 0] - cx) / dq, (q[:, 1] - cy) / dq, (q[:, 2] - cX) / dt, (q[:, 3] - cY) / dt
+    one, zero = torch.ones_like(x), torch.zeros_like(x)
+    ra = torch.stack([x, y, one, zero, zero, zero, -(X * x), -(X * y)], dim=1)
+    rb = torch.stack([zero, zero, zero, x, y, one, -(Y * x), -(Y * y)], dim=1)
+    A = torch.stack([ra, rb], dim=1).reshape(-1, 8)
+    b = torch.stack([X, Y], dim=1).reshape(-1, 1)
+    return A, b
+
+
+def denormalise(hn, box):
+    """H [3, 3] of the normalised solution hn [8] (step 5 of the fit's definition, in numpy)."""
+    cx, cy, dq, cX, cY, dt = (float(v) for v in box)
+    Hn = np.append(np.asarray(hn, dtype=np.float64), 1.0).reshape(3, 3)
+    Tq = np.array([[1 / dq, 0, -cx / dq], [0, 1 / dq, -cy / dq], [0, 0, 1.0]])
+    Tt = np.array([[dt, 0, cX], [0, dt, cY], [0, 0, 1.0]])
+    F = Tt @ Hn @ Tq
+    return F / F[2, 2]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--width", type=int, default=3840)
@@ -63,6 +94,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--chunk-mib", type=int, default=1024, help="torch arm: size of one [c, 3, M] product")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "verify_time_4k_o4_s5.json"))
+    ap.add_argument("--refit-rounds", type=int, default=4)
+    ap.add_argument("--refit-out", default=os.path.join(ROOT, "profiles", "refit_time_4k_o4_s5.json"))
     args = ap.parse_args()
     dx, dy = args.shift
     top = 1 << (args.octaves - 1)
@@ -98,6 +131,13 @@ def main():
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t2 = args.thresh * args.thresh
 
+        L = sift_amd.lib()
+        d_inl = torch.zeros(max(M, 1), dtype=torch.int32, device=dev)
+        refined, n_in, n_rounds = sift_amd.Homography(), ctypes.c_size_t(), ctypes.c_int32()
+        r0, r1, r2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+        refit_rows, refit_info = [], {}
+        torch.cuda.synchronize()
+
         diff = None
         for it in range(args.warmup + args.steps):
             H, best, inl = a.verify_features(b, pairs, K, args.ransac_seed, args.thresh)
@@ -111,6 +151,33 @@ def main():
             torch.cuda.synchronize()
             if it >= args.warmup:
                 rows.append(dict(t, torch_score_ms=e0.elapsed_time(e1)))
+            # the refit arm, then torch's least squares of the system of the refit's last list
+            start = sift_amd.Homography((ctypes.c_double * 9)(*H.reshape(9)), int(best), 0)
+            rc = L.sift_homography_refit_device(a._h, xy.data_ptr(), M, ctypes.byref(start), args.thresh,
+                                                args.refit_rounds, ctypes.byref(refined), ctypes.byref(n_rounds),
+                                                d_inl.data_ptr(), M, ctypes.byref(n_in))
+            if rc:
+                raise RuntimeError("sift_homography_refit_device: %d" % rc)
+            rt = a.refit_timings()
+            box, _ = a.homography_fit_sums()
+            row = dict(fit_ms=rt["fit_ms"], rescore_ms=rt["rescore_ms"], rounds=int(n_rounds.value))
+            try:
+                r0.record()
+                A, rhs = torch_system(torch, xy, d_inl[:n_in.value].long(), box)
+                r1.record()
+                sol = torch.linalg.lstsq(A, rhs).solution
+                r2.record()
+                torch.cuda.synchronize()
+                row.update(torch_system_ms=r0.elapsed_time(r1), torch_lstsq_ms=r1.elapsed_time(r2))
+                if not refit_info:
+                    Ht = denormalise(sol.cpu().numpy().reshape(8), box)
+                    Hr = np.array(refined.h, dtype=np.float64).reshape(3, 3)
+                    refit_info["torch_lstsq_max_abs_diff"] = float(np.abs(Ht - Hr).max())
+                del A, rhs, sol
+            except RuntimeError as e:   # a torch build without a device lstsq driver for this shape
+                refit_info["torch_lstsq_error"] = str(e).splitlines()[0][:200]
+            if it >= args.warmup:
+                refit_rows.append(row)
             if diff is None:
                 d = np.abs(tc.cpu().numpy() - np.maximum(counts, 0))[counts >= 0]
                 diff = dict(torch_counts_equal=int((d == 0).sum()), torch_counts_max_abs_diff=int(d.max(initial=0)))
@@ -131,6 +198,25 @@ def main():
     print(line)
     if args.out:
         with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+    keys = [k for k in refit_rows[0] if all(k in r for r in refit_rows)]
+    ref = {k: round(statistics.median(r[k] for r in refit_rows), 4) for k in keys}
+    Hr = np.array(refined.h, dtype=np.float64).reshape(3, 3)
+    shift = np.array([[1.0, 0, -dx], [0, 1.0, -dy], [0, 0, 1.0]])
+    ref.update(image=out["image"], octaves=args.octaves, scales=args.scales, seed=args.seed, shift=[dx, dy],
+               steps=args.steps, warmup=args.warmup, pairs=M, thresh=args.thresh, max_rounds=args.refit_rounds,
+               start_inliers=len(inl), refit_inliers=int(n_in.value), start_max_abs_error=err,
+               refit_max_abs_error=float(np.abs(Hr - shift).max()), score_ms=out["score_ms"],
+               select_ms=out["select_ms"], hypotheses=K,
+               fit_over_score=round(ref["fit_ms"] / out["score_ms"], 4) if out["score_ms"] > 0 else None,
+               **refit_info)
+    if "torch_lstsq_ms" in ref and ref["fit_ms"] > 0:
+        ref["torch_lstsq_over_fit"] = round(ref["torch_lstsq_ms"] * ref["rounds"] / ref["fit_ms"], 1)
+    line = json.dumps(ref)
+    print(line)
+    if args.refit_out:
+        with open(args.refit_out, "w") as f:
             f.write(line + "\n")
 
 
