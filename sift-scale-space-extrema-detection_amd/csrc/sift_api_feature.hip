@@ -14,14 +14,14 @@ static_assert(kDescOri == SIFT_DESC_ORI && kDescBytes == SIFT_DESC_BYTES && kDes
 // What the two stages need of the pyramid, whoever supplies the keypoints (sift_set_keypoints needs no more): one
 // whole image whose octaves all have Gaussian planes.
 static int check_feature_planes(sift_ctx* ctx) {
-  if (ctx->detect_pending || ctx->begin_pending || ctx->dog_source == kNone)
+  if (ctx->detect_pending || ctx->begin_pending || ctx->pyr.dog_source == kNone)
     return set_err(ctx, SIFT_E_STATE, "no pyramid: build or load one first");
   if (ctx->P.nimg > 1) return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors of a batch");
-  if (ctx->row0 != 0 || ctx->own_lo >= 0)
+  if (ctx->shard.row0 != 0 || ctx->shard.own_lo >= 0)
     return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors with a row origin or owned rows");
-  if (ctx->planes_first > ctx->o_first)
+  if (ctx->pyr.planes_first > ctx->pyr.o_first)
     return set_err(ctx, SIFT_E_UNSUPPORTED, "orientations / descriptors of a seed-range detection");
-  if (!ctx->have_gauss) return set_err(ctx, SIFT_E_STATE, "Gaussian planes not materialised");
+  if (!ctx->pyr.have_gauss) return set_err(ctx, SIFT_E_STATE, "Gaussian planes not materialised");
   return SIFT_OK;
 }
 
@@ -49,7 +49,7 @@ int sift_orient(sift_ctx* ctx, sift_orientation* out, size_t cap, size_t* n_out)
       HIPCHK(F.ori_mask.ensure((size_t)n * sizeof(unsigned long long)));
       HIPCHK(F.ori_theta.ensure((size_t)n * kOriMaxPeaks * sizeof(double)));
       HIPCHK(hipEventRecord(F.ev[0], ctx->stream));
-      HIPCHK(launch_orient(ctx->P, ctx->gauss.as<float>(), ctx->planes_first, ctx->kp.as<Keypoint>(), n,
+      HIPCHK(launch_orient(ctx->P, ctx->pyr.gauss.as<float>(), ctx->pyr.planes_first, ctx->kp.as<Keypoint>(), n,
                            F.ori_count.as<unsigned>(), F.ori_mask.as<unsigned long long>(), F.ori_theta.as<double>(),
                            ctx->stream));
       unsigned total = 0;  // the record count sizes the record buffer
@@ -90,7 +90,7 @@ int sift_describe(sift_ctx* ctx, uint8_t* desc, uint8_t* described, size_t cap, 
       HIPCHK(F.desc_n.ensure(sizeof(unsigned)));
       HIPCHK(hipEventRecord(F.ev[2], ctx->stream));
       HIPCHK(hipMemsetAsync(F.desc_n.p, 0, sizeof(unsigned), ctx->stream));
-      HIPCHK(launch_describe(ctx->P, ctx->gauss.as<float>(), ctx->planes_first, ctx->kp.as<Keypoint>(),
+      HIPCHK(launch_describe(ctx->P, ctx->pyr.gauss.as<float>(), ctx->pyr.planes_first, ctx->kp.as<Keypoint>(),
                              F.ori.as<Orientation>(), (int)n, F.desc.as<unsigned char>(),
                              F.desc_ok.as<unsigned char>(), F.desc_n.as<unsigned>(), ctx->stream));
       HIPCHK(hipEventRecord(F.ev[3], ctx->stream));
@@ -138,7 +138,7 @@ int sift_set_keypoints(sift_ctx* ctx, const sift_keypoint* kp, size_t n) {
   if (!count_ok(n)) return set_err(ctx, SIFT_E_ARG, "too many keypoints");  // the scan runs over n + 1
   const Pyramid& P = ctx->P;
   for (size_t i = 0; i < n; ++i) {
-    if (kp[i].octave < ctx->planes_first || kp[i].octave >= P.O)
+    if (kp[i].octave < ctx->pyr.planes_first || kp[i].octave >= P.O)
       return set_err(ctx, SIFT_E_ARG, "keypoint octave out of range");
     if (kp[i].scale_level < 0 || kp[i].scale_level >= P.NS)
       return set_err(ctx, SIFT_E_ARG, "keypoint scale_level out of range");
@@ -152,9 +152,9 @@ int sift_set_keypoints(sift_ctx* ctx, const sift_keypoint* kp, size_t n) {
   F.have_ori = F.have_desc = false;
   F.n_ori = F.n_desc_ok = 0;
   // nothing of the refinement this list replaces is served afterwards
-  ctx->n_sing = 0;
-  ctx->has_origins = false;
-  ctx->blk_counts.clear();
+  ctx->ref.n_sing = 0;
+  ctx->shard.has_origins = false;
+  ctx->ref.blk_counts.clear();
   ctx->tm.refine_ms = 0;
   F.orient_ms = F.describe_ms = 0;
   return SIFT_OK;

@@ -112,14 +112,14 @@ __device__ __forceinline__ void x_centre(const XWin<NP>& Wn, XUnit<NP>& U, const
                          (unsigned)(U.xw * kXW - 1 + U.lane);
     unsigned long long lowmask, ambmask;
     const unsigned long long bit =
-        x_row_decide(v, nmax, nmin, U.colmask, L.c_lo, L.c_hi, L.exact_planes != 0, key, &L.counters[0],
+        x_row_decide(v, nmax, nmin, U.colmask, L.c_lo, L.c_hi, L.exact_planes != 0, key, &L.counters[kCntAmb],
                      L.ambbitmap ? nullptr : L.amb_keys, L.amb_cap, U.low, lowmask, ambmask);
 
     if (ambmask && L.ambbitmap && U.lane == 0) {  // an ambiguous word (rare): its bits and its index for k_exact_words
       const unsigned long long aw = ambmask >> 1;  // lanes 1..62 -> bits 0..61
       const long long gw = U.word0 + ((long long)(q - 1) * U.h + y) * U.nw + U.xw;
       L.ambbitmap[gw] = aw;
-      atomicAdd(&L.counters[0], (unsigned)__popcll(aw));
+      atomicAdd(&L.counters[kCntAmb], (unsigned)__popcll(aw));
       const unsigned slot = atomicAdd(&L.counters[kAmbWords], 1u);
       if (slot < L.amb_cap) L.amb_keys[slot] = (unsigned)gw;
     }
@@ -206,7 +206,7 @@ __device__ __forceinline__ void x_scan(const Pyramid& P, const ExtremaLaunch& L,
     x_load(U, Wn.raw[0], min(y + 6, y1 + 1));
     x_centre<NP, 1, 2, 0, LOWL>(Wn, U, L, y + 2);
   }
-  if (U.lane == 0 && U.low) atomicAdd(&L.counters[1], U.low);
+  if (U.lane == 0 && U.low) atomicAdd(&L.counters[kCntLow], U.low);
 }
 
 // One wave per unit (octave, strip of kXRows rows, 62-column word, scale
@@ -316,7 +316,7 @@ __global__ __launch_bounds__(256) void k_emit(const Pyramid P, const EmitLaunch 
 // contrast exactly.
 __global__ __launch_bounds__(64) void k_exact_extrema(const Pyramid P, const ExactLaunch X) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
-  const unsigned n_amb = min(X.counters[0], X.amb_cap);
+  const unsigned n_amb = min(X.counters[kCntAmb], X.amb_cap);
   const unsigned n = min(*X.n, X.cap);
   for (unsigned j = blockIdx.x; j < n_amb; j += gridDim.x) {
     const unsigned key = X.amb_keys[j];
@@ -363,16 +363,16 @@ __global__ __launch_bounds__(64) void k_exact_extrema(const Pyramid P, const Exa
       X.keep[idx] = cand ? 1u : 0u;
       X.value[idx] = v;
       if (ext && !cand) {
-        atomicAdd(&X.counters[1], 1u);
+        atomicAdd(&X.counters[kCntLow], 1u);
         if (X.late_keys) {  // decided low contrast here: joins the low-contrast list
-          const unsigned slot = atomicAdd(&X.counters[6], 1u);
+          const unsigned slot = atomicAdd(&X.counters[kCntLowLate], 1u);
           if (slot < X.amb_cap) {
             X.late_keys[slot] = key;
             X.late_vals[slot] = v;
           }
         }
       }
-      if (!cand) atomicAdd(&X.counters[2], 1u);  // dropped entries
+      if (!cand) atomicAdd(&X.counters[kCntDrop], 1u);  // dropped entries
     }
     __syncthreads();  // smem is reused by the next key
   }
@@ -438,16 +438,16 @@ __global__ __launch_bounds__(kWordThreads) void k_exact_words(const Pyramid P, c
         X.keep[idx] = cnd ? 1u : 0u;
         X.value[idx] = v;
         if (ext && !cnd) {
-          atomicAdd(&X.counters[1], 1u);
+          atomicAdd(&X.counters[kCntLow], 1u);
           if (X.late_keys) {  // decided low contrast here: joins the low-contrast list
-            const unsigned slot = atomicAdd(&X.counters[6], 1u);
+            const unsigned slot = atomicAdd(&X.counters[kCntLowLate], 1u);
             if (slot < X.amb_cap) {
               X.late_keys[slot] = key;
               X.late_vals[slot] = v;
             }
           }
         }
-        if (!cnd) atomicAdd(&X.counters[2], 1u);  // dropped entries
+        if (!cnd) atomicAdd(&X.counters[kCntDrop], 1u);  // dropped entries
       }
     };
     if (__popcll(amb) <= kWordPixelMax) {

@@ -841,7 +841,7 @@ __device__ __forceinline__ void fused_decide(const Pyramid& P, const GaussLaunch
     unsigned long long lowmask;  // the low-contrast list is not fused (build_common)
     const unsigned long long bit =
         x_row_decide(v, nmax, nmin, colmask, L.X.c_lo, L.X.c_hi, false, key0 + (unsigned)y * (unsigned)T.w,
-                     &L.X.counters[0], L.X.amb_keys, L.X.amb_cap, low, lowmask, ambmask);
+                     &L.X.counters[kCntAmb], L.X.amb_keys, L.X.amb_cap, low, lowmask, ambmask);
     const unsigned long long word = bit >> 1;  // lanes 1..kFX -> bits 0..kFX-1
     if (l == 0) {
       const long long row = (long long)(t - 1) * T.h + y;
@@ -1071,7 +1071,7 @@ __global__ __launch_bounds__(256, OCT0 ? SIFT_W0 : SIFT_MINW1) void k_gauss_dog(
       for (int q = 0; q < 4; ++q) lprev[i][q] = out[i][q];
   }
   if constexpr (XF) {
-    if (T.lane == 0 && xlow) atomicAdd(&L.X.counters[1], xlow);
+    if (T.lane == 0 && xlow) atomicAdd(&L.X.counters[kCntLow], xlow);
   }
 }
 

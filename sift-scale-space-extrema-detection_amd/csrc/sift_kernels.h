@@ -26,7 +26,7 @@ struct FusedExtrema {
   unsigned* rowcount;          // (scale 1, row 0) of the octave: [S][h]
   int nw;                      // words per row (= tile columns of the launch)
   unsigned* amb_keys;          // keys needing an exact fp64 decision
-  unsigned* counters;          // [0] ambiguous, [1] low-contrast
+  unsigned* counters;          // kCntAmb, kCntLow (below)
   unsigned amb_cap;
   float c_lo, c_hi;            // fp32 contrast thresholds (see ExtremaLaunch)
 };
@@ -97,7 +97,7 @@ struct ExtremaLaunch {
   unsigned long long* bitmap;
   unsigned* rowcount;
   unsigned* amb_keys;            // keys needing an exact fp64 decision (unordered)
-  unsigned* counters;            // [0] ambiguous, [1] low-contrast, [2] dropped by exact pass
+  unsigned* counters;            // kCntAmb, kCntLow, kCntDrop (below)
   unsigned amb_cap;
   unsigned long long* lowbitmap; // certain low-contrast extrema, same layout as bitmap (nullptr = not listed)
   unsigned* lowrowcount;
@@ -108,6 +108,24 @@ struct ExtremaLaunch {
   unsigned long long* ambbitmap;
 };
 constexpr int kAmbWords = 8;     // counters slot: listed ambiguous words
+// The other slots of the device counters (sift_ctx::counters), written by the
+// extrema and refinement kernels and read back by the host.
+enum {
+  kCntAmb = 0,       // ambiguous keys
+  kCntLow = 1,       // low-contrast extrema
+  kCntDrop = 2,      // slots dropped by the exact pass
+  kCntUnc = 3,       // uncertain refinements
+  kCntSing = 4,      // singular Hessians
+  kCntLowLate = 6,   // late (exact-pass) low-contrast entries
+  kCntLowSure = 7,   // ordered (certain) low-contrast entries
+  kCntN = 12,        // candidate slots
+  kCntKp = 13,       // keypoints
+  kCntDbg = 16,      // debug block, kCntDbgWords slots: [kCntDbg + b] refinements uncertain for reason b
+  kCntDbgIter = 22,  // ... [kCntDbgIter + min(it, 4)] by iteration count
+  kCntDbgPrec = 27,  // ... uncertain for output precision
+  kCntDbgWords = 16,
+  kBlk = 64          // from here: the kept keypoints per (octave, scale) block (kBlkWords slots, below)
+};
 
 // One launch over every octave: global row g (one wave each) = G.row_off[o] +
 // (s-1) h_o + y.
@@ -133,14 +151,14 @@ hipError_t launch_fill_values(const Pyramid& P, const unsigned* keys, double* va
                               hipStream_t st);
 
 struct ExactLaunch {
-  const unsigned* amb_keys;      // counters[0] of them (at most amb_cap stored)
+  const unsigned* amb_keys;      // counters[kCntAmb] of them (at most amb_cap stored)
   unsigned amb_cap;
   const unsigned* keys;          // ordered candidates
   const unsigned* n;             // device: number of candidates
   unsigned cap;
   unsigned* keep;
   double* value;
-  unsigned* counters;            // [6]: late low-contrast extrema (ambiguous ones decided low)
+  unsigned* counters;            // kCntLowLate: late low-contrast extrema (ambiguous ones decided low)
   unsigned* late_keys;           // their keys / exact values (nullptr = not listed), amb_cap slots
   double* late_vals;
   // A key's list position is its row's offset plus the candidate bits before
@@ -268,6 +286,7 @@ static_assert(kBlkN >= kMaxOctaves * kMaxScales, "one image's blocks");
 constexpr int kBlkStart = kBlkN;                  // blk[kBlkStart + b], b <= O*S: first slot of block b
 constexpr int kBlkUnsorted = kBlkStart + kBlkN + 1;
 constexpr int kBlkWords = kBlkUnsorted + 1;
+constexpr int kCntAll = kBlk + kBlkWords;  // all counter slots: per-block counts, block starts, order flag
 hipError_t launch_scatter_keys(const unsigned* keep, const unsigned* pos, const unsigned* key, const unsigned* n,
                                int cap, unsigned* out, hipStream_t st);
 // The keep flags, their exclusive scan into pos and the kept keypoints'

@@ -90,8 +90,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
       if (R.uncertain) {
         unc = true;
         for (int b = 0; b < 6; ++b)
-          if ((R.why >> b) & 1u) atomicAdd(&L.counters[16 + b], 1u);
-        atomicAdd(&L.counters[22 + min(it, 4)], 1u);
+          if ((R.why >> b) & 1u) atomicAdd(&L.counters[kCntDbg + b], 1u);
+        atomicAdd(&L.counters[kCntDbgIter + min(it, 4)], 1u);
         break;
       }
       if (R.state == 3) { status = kRefSingular; break; }
@@ -103,7 +103,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
           k.scale_level = s;
           k.local_y = m;
           k.local_x = n;
-          atomicAdd(&L.counters[27], 1u);
+          atomicAdd(&L.counters[kCntDbgPrec], 1u);
           break;
         }
         status = kRefKeep;
@@ -113,13 +113,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void k
       s = R.s; m = R.m; n = R.n;
     }
     L.status[i] = unc ? kRefUncertain : status;
-    if (!unc && status == kRefSingular) atomicAdd(&L.counters[4], 1u);
+    if (!unc && status == kRefSingular) atomicAdd(&L.counters[kCntSing], 1u);
   }
   const unsigned long long mask = __ballot(unc);
   if (mask) {
     const int leader = __ffsll((long long)mask) - 1;
     unsigned base = 0;
-    if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(&L.counters[3], (unsigned)__popcll(mask));
+    if ((int)(threadIdx.x & 63) == leader) base = atomicAdd(&L.counters[kCntUnc], (unsigned)__popcll(mask));
     base = __shfl(base, leader);
     const unsigned pre = __builtin_amdgcn_mbcnt_hi((unsigned)(mask >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mask, 0u));
     if (unc) L.uncertain[base + pre] = (unsigned)i | (polish ? kPolish : 0u);
@@ -141,7 +141,7 @@ template <int NT>
 __global__ __launch_bounds__(NT) void k_refine_exact(const Pyramid P, const RefineLaunch L) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   __shared__ int pos[4];
-  const unsigned nu = min(L.counters[3], (unsigned)L.cap);
+  const unsigned nu = min(L.counters[kCntUnc], (unsigned)L.cap);
   for (unsigned j = blockIdx.x; j < nu; j += gridDim.x) {
     const unsigned e = L.uncertain[j];
     const unsigned i = e & ~kPolish;
@@ -200,7 +200,7 @@ __global__ __launch_bounds__(NT) void k_refine_exact(const Pyramid P, const Refi
     }
     if (threadIdx.x == 0) {
       L.status[i] = status;
-      if (status == kRefSingular) atomicAdd(&L.counters[4], 1u);
+      if (status == kRefSingular) atomicAdd(&L.counters[kCntSing], 1u);
     }
   }
 }
