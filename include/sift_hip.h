@@ -814,6 +814,90 @@ int sift_verify_features_refit(struct sift_ctx *ctx, struct sift_ctx *train_ctx,
  * (flags, scan, read-back, emission).  Both 0 when no round was tried. */
 int sift_last_refit_timings(struct sift_ctx *ctx, double *fit_ms, double *rescore_ms);
 
+/* ---- Homography warp ----------------------------------------------------------
+ *
+ * The product at the far end of the path: an image resampled through a
+ * homography, gray (fp32) or RGBA (4 x uint8).  Like the stages above it is
+ * defined with + - * /, comparisons and floor in fp64 with no contraction and no
+ * other library function, and it is bit-identical from run to run.  These entry
+ * points are detected by symbol; SIFT_ABI_VERSION stays 9.
+ *
+ * Inverse of h (row-major).  The adjugate a, term by term:
+ *   a[0] = h4*h8 - h5*h7, a[1] = h2*h7 - h1*h8, a[2] = h1*h5 - h2*h4,
+ *   a[3] = h5*h6 - h3*h8, a[4] = h0*h8 - h2*h6, a[5] = h2*h3 - h0*h5,
+ *   a[6] = h3*h7 - h4*h6, a[7] = h1*h6 - h0*h7, a[8] = h0*h4 - h1*h3;
+ *   d = (h0*a[0] + h1*a[3]) + h2*a[6];  out[i] = a[i] / d.
+ * When d is zero or not finite, or any out[i] is not finite, there is no inverse:
+ * nine zeros (the "none" model above, all zeros, is such a case).  It is the true
+ * inverse, not the adjugate: the sign of the third row survives a mirroring h
+ * (det < 0), and the rule below tests w > 0.
+ *
+ * The warp takes m[9], which maps a DESTINATION pixel to a SOURCE position; it
+ * inverts nothing.  To bring the query image into the train frame, pass the
+ * inverse of the model's h.  The matrix is not validated: NaN, infinite and huge
+ * entries are defined by the rule (no pixel valid, or few).
+ *
+ * Per destination pixel (X, Y), 0 <= X < dst_w, 0 <= Y < dst_h as doubles, and a
+ * source of sw x sh pixels p (pixel centres at integer coordinates, as abs_x and
+ * abs_y of sift_keypoint are; pixel values converted to fp64):
+ *   u = (m0*X + m1*Y) + m2, v = (m3*X + m4*Y) + m5, w = (m6*X + m7*Y) + m8;
+ *   r = 1.0 / w, sx = u * r, sy = v * r                      (one division);
+ *   valid iff w > 0 && sx >= 0 && sy >= 0 && sx <= sw-1 && sy <= sh-1
+ *     (any NaN compares false; the test precedes every cast to an integer, and
+ *     an invalid pixel reads nothing);
+ *   x0 = min(floor(sx), max(sw-2, 0)), x1 = min(x0+1, sw-1), fx = sx - x0,
+ *   gx = 1.0 - fx;  y0, y1, fy, gy likewise from sy and sh;
+ *   top = p(y0,x0)*gx + p(y0,x1)*fx,  bot = p(y1,x0)*gx + p(y1,x1)*fx,
+ *   val = top*gy + bot*fy            (every product rounded, then added).
+ * The clamp of x0 makes sx == sw-1 legal, with fx = 1; a source one pixel wide
+ * gives x0 = x1 = 0 and fx = 0.
+ *  Gray: dst = (float)val, rounded once.  RGBA: each of the four channels is
+ *  interpolated on its byte values, dst = floor(val + 0.5); val lies in
+ *  [0, 255], so nothing clamps.  An invalid pixel receives the caller's fill:
+ *  a float, bits as given, or four bytes.
+ *  SIFT_WARP_NEAREST: xn = floor(sx + 0.5), yn = floor(sy + 0.5) under the same
+ *  validity test and dst = p(yn, xn) unchanged, for masks and label images.
+ *  Mask (optional): one byte per destination pixel, dense (dst_w * dst_h), 1 for
+ *  a valid pixel and 0 for an invalid one.  *n_valid (optional): the number of
+ *  valid pixels, an integer sum.
+ * With m the identity or an integer translation gx or fx is exactly 0 or 1, and a
+ * source without negative zeros or non-finite values comes back byte for byte
+ * where it is valid.  A -0.0 comes back as +0.0 and inf * 0 is a NaN.
+ *
+ * Limits: ctx, source, destination, matrix (and the RGBA fill) non-NULL, every
+ * dimension > 0, width * height < 2^31 on either side, strides >= the width, an
+ * RGBA stride a multiple of 4, RGBA device images 4-byte aligned, a mode named
+ * below, and a destination that is not the source (they must not overlap): else
+ * SIFT_E_ARG, nothing written. */
+enum { SIFT_WARP_NEAREST = 0, SIFT_WARP_BILINEAR = 1 };
+
+/* Host math, no context.  SIFT_E_ARG with nine zeros in out when h has no
+ * inverse (above), or when h is NULL. */
+int sift_homography_inverse(const double h[9], double out[9]);
+
+/* Device images, strides in pixels; m in host memory.  d_mask (device, dense) and
+ * n_valid (host) may be NULL.  Ordered on ctx's stream and complete on return;
+ * nothing is copied but the count, and not that when n_valid is NULL. */
+int sift_warp_gray_device(struct sift_ctx *ctx, const float *d_src, int src_w, int src_h, size_t src_stride_px,
+                          const double m[9], int mode, float fill, float *d_dst, int dst_w, int dst_h,
+                          size_t dst_stride_px, uint8_t *d_mask, size_t *n_valid);
+/* The same with host images, through the context's own device buffers; only the
+ * dst_w pixels of each destination row are written.  A buffer that is dense and
+ * page-locked (sift_host_register) moves in one DMA. */
+int sift_warp_gray(struct sift_ctx *ctx, const float *src, int src_w, int src_h, size_t src_stride_px,
+                   const double m[9], int mode, float fill, float *dst, int dst_w, int dst_h, size_t dst_stride_px,
+                   uint8_t *mask, size_t *n_valid);
+/* RGBA: four bytes per pixel, strides in bytes, fill = four bytes. */
+int sift_warp_rgba_device(struct sift_ctx *ctx, const uint8_t *d_src, int src_w, int src_h, size_t src_stride_bytes,
+                          const double m[9], int mode, const uint8_t fill[4], uint8_t *d_dst, int dst_w, int dst_h,
+                          size_t dst_stride_bytes, uint8_t *d_mask, size_t *n_valid);
+int sift_warp_rgba(struct sift_ctx *ctx, const uint8_t *src, int src_w, int src_h, size_t src_stride_bytes,
+                   const double m[9], int mode, const uint8_t fill[4], uint8_t *dst, int dst_w, int dst_h,
+                   size_t dst_stride_bytes, uint8_t *mask, size_t *n_valid);
+
+/* Device time of the last warp's kernel on ctx, milliseconds. */
+int sift_last_warp_timing(struct sift_ctx *ctx, double *warp_ms);
+
 /* Wait for all work queued on ctx's stream. */
 int sift_synchronize(struct sift_ctx *ctx);
 

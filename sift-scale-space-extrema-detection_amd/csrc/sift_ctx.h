@@ -1,6 +1,6 @@
 // The context behind the C ABI, its state grouped by stage, and what its host files share: sift_api.hip (lifetime,
 // shared helpers), sift_api_pyramid / _extrema / _detect / _shard / _image.hip (detection) and sift_api_feature /
-// _match / _verify / _refit.hip (later stages).  No kernel file includes this.
+// _match / _verify / _refit / _warp.hip (later stages).  No kernel file includes this.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -106,6 +106,14 @@ struct RefitState {
   bool have_fit = false;                       // rec holds a fit (box and sums included)
   EventSet<3> ev;                              // a round: before the fit [0], after it [1], after the rescoring [2]
   double fit_ms = 0, rescore_ms = 0;
+};
+
+// Homography warp (sift_api_warp.hip).
+struct WarpState {
+  DBuf src, dst, mask;                         // host-form staging: the source, the destination, the mask (all dense)
+  DBuf count;                                  // the last counted warp: its valid pixels, then one word per block
+  EventSet<2> ev;                              // around the kernels
+  double warp_ms = 0;
 };
 
 // Taps of the deepest schedule built so far (setup_geometry): per-(octave, scale) sigma, the padded tap vector, its
@@ -294,6 +302,7 @@ struct sift_ctx {
   sift::MatchState match;
   sift::VerifyState verify;
   sift::RefitState refit;
+  sift::WarpState warp;
   HBuf hscratch;                   // pinned: one sift::StageScratch (sift_ctx_create)
   DBuf counters, temp;             // kCntAll counter slots (sift_kernels.h); scan scratch
   HBuf h_counters;                 // pinned mirror of counters

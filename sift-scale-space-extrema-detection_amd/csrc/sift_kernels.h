@@ -517,4 +517,16 @@ int plane_image_parts(long long n);
 hipError_t launch_plane_image(const float* plane, long long n, int mode, double coefficient, float2* parts,
                               unsigned* out, hipStream_t st);
 
+// Homography warp (sift_warp.hip; the definition is in include/sift_hip.h).  m: nine host doubles, destination
+// pixel -> source position; strides in pixels (an RGBA pixel is one word); mask (dense, dw * dh bytes) and count
+// (one word, set to the valid pixels) may be nullptr; partial: kWarpMaxBlocks words of scratch, used when count is
+// given.  0 < dw * dh < 2^31.
+constexpr int kWarpMaxBlocks = 4096;  // blocks of one warp launch: two rounds of 8 blocks on each of 256 CUs
+hipError_t launch_warp_gray(const float* src, int sw, int sh, size_t sstride_px, const double* m, bool bilinear,
+                            float fill, float* dst, int dw, int dh, size_t dstride_px, unsigned char* mask,
+                            unsigned* partial, unsigned* count, hipStream_t st);
+hipError_t launch_warp_rgba(const unsigned* src, int sw, int sh, size_t sstride_px, const double* m, bool bilinear,
+                            unsigned fill, unsigned* dst, int dw, int dh, size_t dstride_px, unsigned char* mask,
+                            unsigned* partial, unsigned* count, hipStream_t st);
+
 }  // namespace sift

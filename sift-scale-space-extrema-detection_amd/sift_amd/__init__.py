@@ -40,6 +40,9 @@ DISPLAY_PLAIN = 0
 DISPLAY_SIGMOID = 1
 DISPLAY_SAMPLED = 2
 
+WARP_NEAREST = 0
+WARP_BILINEAR = 1
+
 # Exported symbols, exactly those include/sift_hip.h declares.
 ABI_SYMBOLS = (
     "sift_abi_version", "sift_params_default", "sift_ctx_create", "sift_ctx_destroy",
@@ -69,6 +72,8 @@ ABI_SYMBOLS = (
     "sift_homography_fit_device", "sift_homography_fit", "sift_copy_homography_fit_sums",
     "sift_homography_refit_device", "sift_homography_refit", "sift_verify_features_refit",
     "sift_last_refit_timings",
+    "sift_homography_inverse", "sift_warp_gray_device", "sift_warp_gray", "sift_warp_rgba_device", "sift_warp_rgba",
+    "sift_last_warp_timing",
 )
 
 
@@ -252,6 +257,16 @@ def lib():
         "sift_verify_features_refit": (ctypes.c_int, [vp, vp, vp, sz, sz, ctypes.c_uint64, ctypes.c_double,
                                                       ctypes.c_int, hp, ctypes.POINTER(ctypes.c_int32), vp, sz, szp]),
         "sift_last_refit_timings": (ctypes.c_int, [vp, dp, dp]),
+        "sift_homography_inverse": (ctypes.c_int, [dp, dp]),
+        "sift_warp_gray_device": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, sz, dp, ctypes.c_int,
+                                                 ctypes.c_float, vp, ctypes.c_int, ctypes.c_int, sz, vp, szp]),
+        "sift_warp_gray": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, sz, dp, ctypes.c_int, ctypes.c_float,
+                                          vp, ctypes.c_int, ctypes.c_int, sz, vp, szp]),
+        "sift_warp_rgba_device": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, sz, dp, ctypes.c_int, vp, vp,
+                                                 ctypes.c_int, ctypes.c_int, sz, vp, szp]),
+        "sift_warp_rgba": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, sz, dp, ctypes.c_int, vp, vp,
+                                          ctypes.c_int, ctypes.c_int, sz, vp, szp]),
+        "sift_last_warp_timing": (ctypes.c_int, [vp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -286,6 +301,24 @@ def octave_dims(width, height, num_octaves):
     if rc:
         raise SiftError(rc, "sift_octave_dims")
     return [(int(d[2 * o]), int(d[2 * o + 1])) for o in range(num_octaves)]
+
+
+def homography_inverse(H):
+    """The inverse of H [3, 3] by the adjugate formulas of include/sift_hip.h
+    (sift_homography_inverse): float64 [3, 3], or None when H has none."""
+    h = np.ascontiguousarray(H, dtype=np.float64).reshape(9)
+    out = np.zeros(9, dtype=np.float64)
+    dp = ctypes.POINTER(ctypes.c_double)
+    rc = lib().sift_homography_inverse(h.ctypes.data_as(dp), out.ctypes.data_as(dp))
+    return None if rc else out.reshape(3, 3)
+
+
+def float_fill(fill):
+    """fill as a ctypes.c_float: a np.float32 keeps its bits (a NaN's payload, the
+    sign of a zero), anything else is converted."""
+    if isinstance(fill, np.float32):
+        return ctypes.c_float.from_buffer_copy(fill.tobytes())
+    return ctypes.c_float(float(fill))
 
 
 class Context:
@@ -991,6 +1024,42 @@ class Context:
         self._check(self._L.sift_last_refit_timings(self._h, ctypes.byref(a), ctypes.byref(b)),
                     "sift_last_refit_timings")
         return dict(fit_ms=a.value, rescore_ms=b.value)
+
+    # -- homography warp ----------------------------------------------------------
+    def _warp(self, fn, src, per_px, m, mode, fill, dst):
+        """per_px: stride units per pixel (1: pixels, gray; 4: bytes, RGBA)."""
+        oh, ow = dst.shape[0], dst.shape[1]
+        mm = np.ascontiguousarray(m, dtype=np.float64).reshape(9)
+        mask = np.empty((oh, ow), dtype=np.uint8)
+        n = ctypes.c_size_t()
+        self._check(fn(self._h, self._ptr(src), src.shape[1], src.shape[0], src.shape[1] * per_px,
+                       mm.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(mode), fill, self._ptr(dst), ow, oh,
+                       ow * per_px, self._ptr(mask), ctypes.byref(n)), fn.__name__)
+        return dst, mask, int(n.value)
+
+    def warp_gray(self, img, m, out_shape, mode=WARP_BILINEAR, fill=0.0):
+        """img fp32 (H, W) resampled through m [3, 3], which maps a destination
+        pixel to a source position, into out_shape = (rows, columns)
+        (sift_warp_gray): (dst fp32, mask uint8: 1 = valid, valid pixels).  An
+        invalid pixel receives `fill` (a np.float32 keeps its bits)."""
+        a = np.ascontiguousarray(img, dtype=np.float32)
+        dst = np.empty((int(out_shape[0]), int(out_shape[1])), dtype=np.float32)
+        return self._warp(self._L.sift_warp_gray, a, 1, m, mode, float_fill(fill), dst)
+
+    def warp_rgba(self, rgba, m, out_shape, mode=WARP_BILINEAR, fill=(0, 0, 0, 0)):
+        """rgba uint8 (H, W, 4) resampled as warp_gray does, each channel on its
+        byte values (sift_warp_rgba): (dst uint8 (rows, columns, 4), mask,
+        valid pixels).  fill: four bytes."""
+        a = np.ascontiguousarray(rgba, dtype=np.uint8)
+        f = np.broadcast_to(np.asarray(fill, dtype=np.uint8), (4,)).copy()
+        dst = np.empty((int(out_shape[0]), int(out_shape[1]), 4), dtype=np.uint8)
+        return self._warp(self._L.sift_warp_rgba, a, 4, m, mode, self._ptr(f), dst)
+
+    def warp_timing(self):
+        """Device ms of the last warp's kernel."""
+        a = ctypes.c_double()
+        self._check(self._L.sift_last_warp_timing(self._h, ctypes.byref(a)), "sift_last_warp_timing")
+        return a.value
 
     def stream(self):
         return self._L.sift_stream(self._h)
