@@ -1,5 +1,5 @@
 // C ABI of the Gaussian + DoG pyramid: geometry, schedule and taps, the build (build_common, which every detection
-// starts with), plane read-back and caller-supplied planes.  Kernels: sift_gauss.hip.
+// starts with), plane read-back and caller-supplied planes.  Kernels: sift_gauss_*.hip.
 #include "sift_ctx.h"
 
 using namespace sift;

@@ -225,7 +225,7 @@ constexpr size_t kGaussMaxLds = 160 * 1024;  // LDS of one gfx950 CU: a plan wit
 constexpr const char* kGaussFusedName = "k_gauss_dog<octave0,fused extrema>";
 struct GaussPlan {
   GaussPath path;
-  int kernel;              // the instantiation (sift_gauss.hip)
+  int kernel;              // the instantiation (GaussKernel, sift_gauss_dev.h)
   const char* kname;       // its launches, e.g. "k_gauss_rw<12>" or "k_gauss_vert + k_gauss_dog<64>" (static string;
                            // sift_last_pass_kernels); a fused launch is kGaussFusedName
   int rw;                  // k_gauss_rw: window radius RW (12, 16, 24); 0 otherwise

@@ -1,6 +1,6 @@
 // Wave-level pieces of the 26-neighbour extrema decision (gfx950), shared by
 // the extrema scan (k_extrema, sift_extrema.hip) and the decisions fused into
-// the Gaussian+DoG pass (k_gauss_dog, sift_gauss.hip).  One lane per column;
+// the Gaussian+DoG pass (k_gauss_dog, sift_gauss_tile.h).  One lane per column;
 // x-1 / x+1 come from DPP wave shifts.  SIFT_findExtremas, sift.js:212-316:
 // strict 26-neighbour min/max, |v| >= 0.8 thr -> candidate, else low contrast.
 #pragma once
