@@ -898,6 +898,85 @@ int sift_warp_rgba(struct sift_ctx *ctx, const uint8_t *src, int src_w, int src_
 /* Device time of the last warp's kernel on ctx, milliseconds. */
 int sift_last_warp_timing(struct sift_ctx *ctx, double *warp_ms);
 
+/* ---- Keypoint budget -------------------------------------------------------------
+ *
+ * The N strongest keypoints of a list, overall or per cell of a square grid over
+ * the input, chosen on the device.  The definition uses integers alone (one fp64
+ * division and a floor place a record in its cell), so it is exact, does not
+ * depend on how the work is split, and is bit-identical from run to run.  The
+ * list keeps its order: nothing is sorted by strength.  These entry points are
+ * detected by symbol; SIFT_ABI_VERSION stays 9.
+ *
+ * Strength key of record i: the 64 bits of interp_value with the sign bit
+ * cleared, read as an unsigned integer; a NaN has key 0.  For everything that is
+ * not a NaN this orders by |interp_value|: inf is the strongest; +0.0, -0.0 and
+ * NaN are the weakest and equal to each other.  Record i PRECEDES record j when
+ * key_i > key_j, or when key_i == key_j && i < j.
+ *
+ * Cell of record i, when cell_px > 0: ncx = ceil(width / cell_px), ncy =
+ * ceil(height / cell_px); t = abs_x / (double)cell_px;
+ *   ix = t >= 0 ? (t < ncx ? (int)floor(t) : ncx - 1) : 0
+ * (the test comes before the cast; a NaN or a negative coordinate goes to column
+ * 0); iy likewise from abs_y and ncy; cell = iy * ncx + ix.
+ *
+ * Selection, in two steps:
+ *  1. If cell_px > 0 && max_per_cell >= 0, record i survives when fewer than
+ *     max_per_cell records of its cell precede it.  Otherwise every record
+ *     survives.
+ *  2. If max_total >= 0, a survivor is kept when fewer than max_total SURVIVORS
+ *     precede it.  Otherwise every survivor is kept.
+ * The result is the ascending list of the kept indices.
+ *
+ * Limits: n < 2^31 - 1, reserved == 0, cell_px >= 0; with cell_px > 0, width > 0
+ * and height > 0; pointers non-NULL where a count is non-zero: else SIFT_E_ARG.
+ * With cell_px > 0, ncx * ncy <= SIFT_BUDGET_MAX_CELLS: else SIFT_E_UNSUPPORTED.
+ * In both cases nothing is written.
+ *
+ * Not here: radius-based suppression, budgets per octave, budgets for a batch or
+ * for sharded lists, output ordered by strength. */
+typedef struct {
+  int32_t max_total;     /* < 0: no overall limit */
+  int32_t cell_px;       /* 0: no grid; > 0: square cells of cell_px input pixels */
+  int32_t max_per_cell;  /* < 0: no per-cell limit; read only when cell_px > 0 */
+  int32_t reserved;      /* must be 0 */
+} sift_budget;           /* 16 bytes */
+#define SIFT_BUDGET_MAX_CELLS 16384
+
+/* The selection over n device records of a width x height input: *n_out = the
+ * kept count, d_index (device memory, cap indices) the ascending list, or NULL
+ * to only count.  SIFT_E_CAPACITY when cap < *n_out, nothing written.  Any device
+ * array of sift_keypoint will do; of the context only scratch and the timing
+ * change.  Ordered on ctx's stream, complete on return. */
+int sift_keypoint_select_device(struct sift_ctx *ctx, const sift_keypoint *d_kp, size_t n, int width, int height,
+                                const sift_budget *budget, int32_t *d_index, size_t cap, size_t *n_out);
+/* The same with host arrays, through the context's own device buffers. */
+int sift_keypoint_select(struct sift_ctx *ctx, const sift_keypoint *kp, size_t n, int width, int height,
+                         const sift_budget *budget, int32_t *index, size_t cap, size_t *n_out);
+
+/* The selection applied to the context's keypoint list in place, with the
+ * pyramid's input size as width and height: the kept records are gathered in
+ * order into a second buffer, which becomes the list (*n_out = its count; a
+ * pointer that sift_device_keypoints gave before is no longer the list).
+ * Needs a settled keypoint list (a refinement, a detection or
+ * sift_set_keypoints: else SIFT_E_STATE) but no Gaussian planes;
+ * SIFT_E_UNSUPPORTED for a batch, a row origin or owned rows, as sift_orient.
+ * Drops the orientations and descriptors; sift_last_block_counts reports no
+ * blocks and the keypoint origins return SIFT_E_STATE afterwards, as after
+ * sift_set_keypoints.  The singular count and refine_ms stay: they remain true
+ * of the detection.  A second call selects from the already limited list. */
+int sift_limit_keypoints(struct sift_ctx *ctx, const sift_budget *budget, size_t *n_out);
+
+/* The indices into the previous list that the last sift_limit_keypoints kept
+ * (host memory; index == NULL only counts; SIFT_E_CAPACITY: *n_out = required
+ * count).  SIFT_E_STATE when there was no such call, or after a new refinement,
+ * detection or sift_set_keypoints. */
+int sift_copy_keypoint_selection(struct sift_ctx *ctx, int32_t *index, size_t cap, size_t *n_out);
+
+/* Device time of the last selection on ctx through any of the forms above,
+ * milliseconds: the keys, the narrowing passes, the flags, the scan, the count
+ * read-back and the emission. */
+int sift_last_select_timing(struct sift_ctx *ctx, double *select_ms);
+
 /* Wait for all work queued on ctx's stream. */
 int sift_synchronize(struct sift_ctx *ctx);
 

@@ -154,6 +154,7 @@ int sift_set_keypoints(sift_ctx* ctx, const sift_keypoint* kp, size_t n) {
   // nothing of the refinement this list replaces is served afterwards
   ctx->ref.n_sing = 0;
   ctx->shard.has_origins = false;
+  ctx->budget.have_sel = false;
   ctx->ref.blk_counts.clear();
   ctx->tm.refine_ms = 0;
   F.orient_ms = F.describe_ms = 0;

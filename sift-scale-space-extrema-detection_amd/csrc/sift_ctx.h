@@ -1,6 +1,6 @@
 // The context behind the C ABI, its state grouped by stage, and what its host files share: sift_api.hip (lifetime,
 // shared helpers), sift_api_pyramid / _extrema / _detect / _shard / _image.hip (detection) and sift_api_feature /
-// _match / _verify / _refit / _warp.hip (later stages).  No kernel file includes this.
+// _match / _verify / _refit / _warp / _budget.hip (later stages).  No kernel file includes this.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -114,6 +114,19 @@ struct WarpState {
   DBuf count;                                  // the last counted warp: its valid pixels, then one word per block
   EventSet<2> ev;                              // around the kernels
   double warp_ms = 0;
+};
+
+// Keypoint budget (sift_api_budget.hip).
+struct BudgetState {
+  DBuf key, cell;                              // per record: strength key, grid cell
+  DBuf tkey, ttail, rem, hist;                 // per cell: threshold key and tail, quota left; 256 bins
+  DBuf surv, flag, off;                        // per record: step 1's survivors, the kept flags, their scan
+  DBuf in_kp, idx;                             // host-form input records and index list (sift_keypoint_select)
+  DBuf kp2;                                    // sift_limit_keypoints gathers into it, then swaps it with sift_ctx::kp
+  DBuf sel; size_t n_sel = 0;                  // the indices the last sift_limit_keypoints kept,
+  bool have_sel = false;                       // ... while its list is the context's list
+  EventSet<2> ev;                              // around one selection
+  double select_ms = 0;
 };
 
 // Taps of the deepest schedule built so far (setup_geometry): per-(octave, scale) sigma, the padded tap vector, its
@@ -303,7 +316,8 @@ struct sift_ctx {
   sift::VerifyState verify;
   sift::RefitState refit;
   sift::WarpState warp;
-  HBuf hscratch;                   // pinned: one sift::StageScratch (sift_ctx_create)
+  sift::BudgetState budget;
+  HBuf hscratch;                  // pinned: one sift::StageScratch (sift_ctx_create)
   DBuf counters, temp;             // kCntAll counter slots (sift_kernels.h); scan scratch
   HBuf h_counters;                 // pinned mirror of counters
   HBuf hpl;                        // pinned staging of plane reads: two halves, double-buffered
@@ -334,6 +348,6 @@ inline int set_err(sift_ctx* ctx, int code, const std::string& msg) {
 // Drops the results that a new refinement invalidates, and with `candidates` those a new pyramid does.
 inline void drop_results(sift_ctx* ctx, bool candidates) {
   if (candidates) ctx->ext.have_cand = false;
-  ctx->have_kp = ctx->feat.have_ori = ctx->feat.have_desc = false;
+  ctx->have_kp = ctx->feat.have_ori = ctx->feat.have_desc = ctx->budget.have_sel = false;
 }
 

@@ -508,6 +508,30 @@ inline long long fit_chunks(long long m) { return (m + kFitChunk - 1) / kFitChun
 hipError_t launch_homography_fit(const PointPair* points, int n, const int32_t* index, int m, unsigned long long* keys,
                                  double* parts_a, double* parts_b, FitRecord* rec, hipStream_t st);
 
+// Keypoint budget (sift_budget.hip; the definition is in include/sift_hip.h).
+constexpr int kBudgetThreads = 256;
+constexpr int kBudgetPerThread = 8;                                // records of one thread
+constexpr int kBudgetTile = kBudgetThreads * kBudgetPerThread;     // records of one block
+constexpr int kBudgetLdsCells = 16;                                // up to here a block keeps the bins in LDS (16 KiB)
+constexpr int kBudgetMaxCells = 16384;
+// Bytes of the composite behind the key: those of n - 1 (at least one); a selection runs 8 + this many passes.
+int budget_tail_bytes(int n);
+// key[i], and with cell_px > 0 cell[i], of the n records.
+hipError_t launch_budget_keys(const Keypoint* kp, int n, int cell_px, int ncx, int ncy, unsigned long long* key,
+                              unsigned* cell, hipStream_t st);
+// flag[i] = record i is active (active == nullptr: all are) and fewer than quota active records of its cell (cell ==
+// nullptr: one cell) precede it; flag[n] = 0.  tkey, ttail, rem: one word per cell; hist: cells * 256 zeroed words,
+// left zeroed.
+hipError_t launch_budget_select(const unsigned long long* key, const unsigned* cell, const unsigned* active, int n,
+                                int cells, unsigned quota, unsigned long long* tkey, unsigned* ttail, unsigned* rem,
+                                unsigned* hist, unsigned* flag, hipStream_t st);
+// flag[i] = 1 for i < n, flag[n] = 0: a budget without a limit.
+hipError_t launch_budget_fill(unsigned* flag, int n, hipStream_t st);
+// off = the exclusive scan of flag: index[off[i]] = i and kp_out[off[i]] = kp[i] for the flagged records (cap slots;
+// either output may be nullptr).
+hipError_t launch_budget_emit(const unsigned* flag, const unsigned* off, int n, unsigned cap, int32_t* index,
+                              const Keypoint* kp, Keypoint* kp_out, hipStream_t st);
+
 // Image products either side of the path (sift_image.hip).
 // gray/alpha rows are dense (w floats); alpha may be nullptr.
 hipError_t launch_rgba_to_gray(const unsigned char* rgba, size_t stride_bytes, int w, int h, float* gray,

@@ -74,6 +74,8 @@ ABI_SYMBOLS = (
     "sift_last_refit_timings",
     "sift_homography_inverse", "sift_warp_gray_device", "sift_warp_gray", "sift_warp_rgba_device", "sift_warp_rgba",
     "sift_last_warp_timing",
+    "sift_keypoint_select_device", "sift_keypoint_select", "sift_limit_keypoints", "sift_copy_keypoint_selection",
+    "sift_last_select_timing",
 )
 
 
@@ -134,6 +136,21 @@ REFIT_MAX_ROUNDS = 16
 class Homography(ctypes.Structure):
     _fields_ = [("h", ctypes.c_double * 9), ("hypothesis", ctypes.c_int32), ("inliers", ctypes.c_int32)]
 
+
+class Budget(ctypes.Structure):
+    _fields_ = [("max_total", ctypes.c_int32), ("cell_px", ctypes.c_int32), ("max_per_cell", ctypes.c_int32),
+                ("reserved", ctypes.c_int32)]
+
+
+BUDGET_MAX_CELLS = 16384
+
+
+def make_budget(max_total=None, cell_px=0, max_per_cell=None):
+    """sift_budget: None = no limit (stored as -1); cell_px 0 = no grid."""
+    return Budget(-1 if max_total is None else int(max_total), int(cell_px),
+                  -1 if max_per_cell is None else int(max_per_cell), 0)
+
+
 _lib = None
 
 
@@ -153,6 +170,7 @@ def lib():
     fp = ctypes.POINTER(ctypes.c_float)
     pp = ctypes.POINTER(Params)
     hp = ctypes.POINTER(Homography)
+    bp = ctypes.POINTER(Budget)
     sig = {
         "sift_abi_version": (ctypes.c_int, []),
         "sift_params_default": (ctypes.c_int, [pp]),
@@ -267,6 +285,11 @@ def lib():
         "sift_warp_rgba": (ctypes.c_int, [vp, vp, ctypes.c_int, ctypes.c_int, sz, dp, ctypes.c_int, vp, vp,
                                           ctypes.c_int, ctypes.c_int, sz, vp, szp]),
         "sift_last_warp_timing": (ctypes.c_int, [vp, dp]),
+        "sift_keypoint_select_device": (ctypes.c_int, [vp, vp, sz, ctypes.c_int, ctypes.c_int, bp, vp, sz, szp]),
+        "sift_keypoint_select": (ctypes.c_int, [vp, vp, sz, ctypes.c_int, ctypes.c_int, bp, vp, sz, szp]),
+        "sift_limit_keypoints": (ctypes.c_int, [vp, bp, szp]),
+        "sift_copy_keypoint_selection": (ctypes.c_int, [vp, vp, sz, szp]),
+        "sift_last_select_timing": (ctypes.c_int, [vp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -1059,6 +1082,46 @@ class Context:
         """Device ms of the last warp's kernel."""
         a = ctypes.c_double()
         self._check(self._L.sift_last_warp_timing(self._h, ctypes.byref(a)), "sift_last_warp_timing")
+        return a.value
+
+    # -- keypoint budget ----------------------------------------------------------
+    def select_keypoints(self, kp, width, height, max_total=None, cell_px=0, max_per_cell=None):
+        """The ascending indices (int32) of the keypoints of kp (KEYPOINT_DTYPE) that
+        the budget keeps: the max_per_cell strongest of every cell_px x cell_px cell
+        of a width x height input, then the max_total strongest of those; None = no
+        limit (sift_keypoint_select)."""
+        k = np.ascontiguousarray(kp, dtype=KEYPOINT_DTYPE)
+        b = make_budget(max_total, cell_px, max_per_cell)
+        out = np.zeros(max(k.shape[0], 1), dtype=np.int32)
+        n = ctypes.c_size_t()
+        self._check(self._L.sift_keypoint_select(self._h, self._ptr(k), k.shape[0], int(width), int(height),
+                                                 ctypes.byref(b), out.ctypes.data_as(ctypes.c_void_p), out.shape[0],
+                                                 ctypes.byref(n)), "sift_keypoint_select")
+        return out[:n.value]
+
+    def limit_keypoints(self, max_total=None, cell_px=0, max_per_cell=None):
+        """The same budget applied to this context's keypoint list in place, over the
+        pyramid's input size (sift_limit_keypoints): the new count."""
+        b = make_budget(max_total, cell_px, max_per_cell)
+        n = ctypes.c_size_t()
+        self._check(self._L.sift_limit_keypoints(self._h, ctypes.byref(b), ctypes.byref(n)), "sift_limit_keypoints")
+        return int(n.value)
+
+    def keypoint_selection(self):
+        """The indices (int32) into the previous list that the last limit_keypoints()
+        kept (sift_copy_keypoint_selection)."""
+        n = ctypes.c_size_t()
+        self._check(self._L.sift_copy_keypoint_selection(self._h, None, 0, ctypes.byref(n)),
+                    "sift_copy_keypoint_selection")
+        out = np.zeros(max(n.value, 1), dtype=np.int32)
+        self._check(self._L.sift_copy_keypoint_selection(self._h, out.ctypes.data_as(ctypes.c_void_p), out.shape[0],
+                                                         ctypes.byref(n)), "sift_copy_keypoint_selection")
+        return out[:n.value]
+
+    def select_timing(self):
+        """Device ms of the last selection (select_keypoints / limit_keypoints)."""
+        a = ctypes.c_double()
+        self._check(self._L.sift_last_select_timing(self._h, ctypes.byref(a)), "sift_last_select_timing")
         return a.value
 
     def stream(self):
