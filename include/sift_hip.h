@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define SIFT_ABI_VERSION 9
+#define SIFT_ABI_VERSION 10
 
 /* Opaque context (one HIP stream + device-resident pyramids). */
 struct sift_ctx;
@@ -299,6 +299,54 @@ int sift_last_octave_timings(struct sift_ctx *ctx, double *ms, int cap, int *n_o
  * (excluding the NUL); SIFT_E_CAPACITY when cap is too small. */
 int sift_last_pass_kernels(struct sift_ctx *ctx, char *buf, size_t cap, size_t *len);
 
+/* The launch plan of one octave's Gaussian+DoG pass as the last build /
+ * detection launched it (ABI version >= 10): a read-only copy of what the
+ * library decided, for tests that must prove which code they ran.  Nothing
+ * here is an input, and the fields may grow with the kernels. */
+enum { /* sift_gauss_plan_info.kernel: the instantiation */
+  SIFT_GAUSS_K_STAGED8 = 0,       /* k_gauss_dog<octave0>, largest radius <= 8        */
+  SIFT_GAUSS_K_STAGED16 = 1,      /* ... 9..16                                         */
+  SIFT_GAUSS_K_STAGED8_FUSED = 2, /* the same two with fused extrema decisions        */
+  SIFT_GAUSS_K_STAGED16_FUSED = 3,
+  SIFT_GAUSS_K_TILES = 4,         /* k_gauss_dog<64>; also octave 0 on the fp64 base  */
+  SIFT_GAUSS_K_SPLIT_TILES = 5,   /* k_gauss_vert + k_gauss_dog<64>                   */
+  SIFT_GAUSS_K_WINDOW12 = 6,      /* k_gauss_rw<12>                                   */
+  SIFT_GAUSS_K_WINDOW16 = 7,      /* k_gauss_rw<16>, <24>: experiments only           */
+  SIFT_GAUSS_K_WINDOW24 = 8,
+  SIFT_GAUSS_K_STREAMED12 = 9,    /* k_gauss_rw<12,true>: experiments only            */
+  SIFT_GAUSS_K_STREAMED16 = 10,   /* k_gauss_rw<16,true>                              */
+  SIFT_GAUSS_K_STREAMED24 = 11    /* k_gauss_rw<24,true>                              */
+};
+enum { /* sift_gauss_plan_info.path */
+  SIFT_GAUSS_PATH_STAGED0 = 0,     /* octave 0 from the staged input region           */
+  SIFT_GAUSS_PATH_BASE0 = 1,       /* octave 0 on a materialised fp64 upsample        */
+  SIFT_GAUSS_PATH_TILES = 2,       /* 64 x 32 tiles                                   */
+  SIFT_GAUSS_PATH_SPLIT_TILES = 3, /* split vertical pass, then 64 x 32 tiles         */
+  SIFT_GAUSS_PATH_WINDOW = 4,      /* register-window tiles                           */
+  SIFT_GAUSS_PATH_STREAMED = 5     /* ... with the window streamed per scale          */
+};
+#define SIFT_GAUSS_MAX_GROUPS 12
+typedef struct sift_gauss_plan_info {
+  int32_t kernel;             /* SIFT_GAUSS_K_*, as launched (a fused launch: the fused one) */
+  int32_t path;               /* SIFT_GAUSS_PATH_*                                    */
+  int32_t rw;                 /* k_gauss_rw: window radius 12 / 16 / 24; else 0       */
+  int32_t tile_w, tile_rows;  /* output columns x rows per block (unfused)            */
+  int32_t gx, gy;             /* tiles per row, tile rows, as launched (a fused launch
+                                 steps by its own decided columns x rows)             */
+  int32_t G;                  /* scale groups, as launched                            */
+  int32_t gb[SIFT_GAUSS_MAX_GROUPS + 1]; /* group g computes scales gb[g] .. gb[g+1]-1 */
+  int32_t sw;                 /* LDS strip row stride, doubles                        */
+  int32_t zero;               /* a generic-radius body is present                     */
+  int32_t keep_l64;           /* the octave keeps its fp64 Gaussian planes            */
+  int32_t vsplit;             /* the split vertical pass ran first                    */
+  int32_t xcd_band;           /* XCD-banded tile order                                */
+  int32_t vec;                /* 16-byte plane stores, as launched                    */
+  int32_t fused;              /* extrema decisions ran inside this launch             */
+} sift_gauss_plan_info;
+/* SIFT_E_STATE without a pyramid built by this library or for an octave the
+ * last build did not launch; SIFT_E_ARG for an octave out of range. */
+int sift_last_gauss_plan(struct sift_ctx *ctx, int octave, sift_gauss_plan_info *out);
+
 /* Device-to-device copy of the last keypoints into caller device memory
  * (e.g. an RCCL all-gather send buffer), ordered on ctx's stream and
  * completed before return. */
@@ -442,7 +490,7 @@ int sift_copy_next_seed_device(struct sift_ctx *ctx, double *d_dst, size_t cap, 
  * 11 and 12, in fp64 on the context's fp32 Gaussian planes, in octave-local
  * pixel units (x = abs_x / 2^(octave-1), likewise y and sigma; plane =
  * SIFT_PLANE_GAUSS (octave, scale_level)).  Results are bit-identical from
- * run to run.  SIFT_ABI_VERSION stays 9: a caller detects these entry points
+ * run to run.  SIFT_ABI_VERSION stayed 9: a caller detects these entry points
  * by symbol (dlsym / hasattr), not by version.  The constants are fixed;
  * there is no setter. */
 #define SIFT_ORI_LAMBDA 1.5      /* Gaussian window sigma = lambda * sigma; box radius 3 * that */
@@ -531,7 +579,7 @@ int sift_set_orientations(struct sift_ctx *ctx, const sift_orientation *rec, siz
  * `second` alone for exactly one unmasked train row.  The arithmetic is
  * integer (int8 matrix cores): results are exact and do not depend on how the
  * work is split.  Like the feature stages, these entry points are detected by
- * symbol; SIFT_ABI_VERSION stays 9. */
+ * symbol; SIFT_ABI_VERSION stayed 9. */
 struct sift_match {
   int32_t best, second, d2_best, d2_second;
 }; /* 16 bytes; a struct tag, as stat(2)'s: C has one namespace for typedefs and functions, and the
@@ -593,7 +641,7 @@ int sift_last_match_timings(struct sift_ctx *ctx, double *match_ms, double *sele
  * device and bit-identical from run to run.  The definition uses only + - * /
  * and comparisons in fp64 with no contraction (no fused multiply-add) and no
  * sqrt, so that a plain restatement reproduces it bit for bit.  Like the stages
- * above, these entry points are detected by symbol; SIFT_ABI_VERSION stays 9.
+ * above, these entry points are detected by symbol; SIFT_ABI_VERSION stayed 9.
  *
  * Model: H is row-major h[0..8] and maps query to train: (u, v, w) = H (x, y, 1),
  * the image point is (u/w, v/w).
@@ -709,7 +757,7 @@ int sift_last_verify_timings(struct sift_ctx *ctx, double *hypotheses_ms, double
  * negation in fp64 with no contraction, no sqrt and no library function, and it
  * is bit-identical from run to run: the one floating-point sum over a
  * data-dependent list is taken in a fixed tree (step 3).  These entry points
- * are detected by symbol; SIFT_ABI_VERSION stays 9.
+ * are detected by symbol; SIFT_ABI_VERSION stayed 9.
  *
  * Fit of a list I of m >= 4 pair indices (each < n; repeats are legal).  The
  * list order is the summation order; the refit passes ascending indices.
@@ -820,7 +868,7 @@ int sift_last_refit_timings(struct sift_ctx *ctx, double *fit_ms, double *rescor
  * homography, gray (fp32) or RGBA (4 x uint8).  Like the stages above it is
  * defined with + - * /, comparisons and floor in fp64 with no contraction and no
  * other library function, and it is bit-identical from run to run.  These entry
- * points are detected by symbol; SIFT_ABI_VERSION stays 9.
+ * points are detected by symbol; SIFT_ABI_VERSION stayed 9.
  *
  * Inverse of h (row-major).  The adjugate a, term by term:
  *   a[0] = h4*h8 - h5*h7, a[1] = h2*h7 - h1*h8, a[2] = h1*h5 - h2*h4,
@@ -905,7 +953,7 @@ int sift_last_warp_timing(struct sift_ctx *ctx, double *warp_ms);
  * division and a floor place a record in its cell), so it is exact, does not
  * depend on how the work is split, and is bit-identical from run to run.  The
  * list keeps its order: nothing is sorted by strength.  These entry points are
- * detected by symbol; SIFT_ABI_VERSION stays 9.
+ * detected by symbol; SIFT_ABI_VERSION stayed 9.
  *
  * Strength key of record i: the 64 bits of interp_value with the sign bit
  * cleared, read as an unsigned integer; a NaN has key 0.  For everything that is

@@ -158,6 +158,8 @@ int sift::build_common(sift_ctx* ctx, const BuildRequest& q) {
   if (o_first > 0 && !q.seed_host && !q.seed_dev) return set_err(ctx, SIFT_E_ARG, "null seed");
   if (o_first == 0 && q.stride < (size_t)W) return set_err(ctx, SIFT_E_ARG, "stride < width");
   HIPCHK(hipSetDevice(ctx->device));
+  // (the launch records go with the plans that setup_geometry replaces)
+  std::fill(ctx->pyr.glaunch, ctx->pyr.glaunch + kMaxOctaves, GaussLaunched{});
   int rc = setup_geometry(ctx, W, H, p, q.sig, true);
   if (rc) return rc;
   Pyramid& P = ctx->P;
@@ -322,7 +324,7 @@ int sift::build_common(sift_ctx* ctx, const BuildRequest& q) {
     L.base_bs = o == 0 ? 0 : seeds_pi;
     L.l64_bs = P.l64_bstride;
     L.vsplit_bs = Y.vsplit_pi;
-    HIPCHK(launch_gauss_dog(P, plan[o], L, ctx->stream));
+    HIPCHK(launch_gauss_dog(P, plan[o], L, ctx->stream, &Y.glaunch[o]));
     Y.pass_kn[o] = L.fuse ? kGaussFusedName : plan[o].kname;
     if (o == o_first) HIPCHK(hipEventRecord(ctx->ev[kEvOct0], ctx->stream));
     HIPCHK(hipEventRecord(Y.ev_go[o], ctx->stream));
@@ -423,6 +425,34 @@ int sift_get_dims(sift_ctx* ctx, int o, int* rows, int* cols) {
   if (o < 0 || o >= ctx->P.O) return set_err(ctx, SIFT_E_ARG, "octave out of range");
   *rows = ctx->P.oct[o].h;
   *cols = ctx->P.oct[o].w;
+  return SIFT_OK;
+}
+
+int sift_last_gauss_plan(sift_ctx* ctx, int o, sift_gauss_plan_info* out) {
+  if (!ctx || !out) return SIFT_E_ARG;
+  const PyrState& Y = ctx->pyr;
+  if (Y.dog_source != kNative) return set_err(ctx, SIFT_E_STATE, "no pyramid built here");
+  if (o < 0 || o >= ctx->P.O) return set_err(ctx, SIFT_E_ARG, "octave out of range");
+  const GaussPlan& G = Y.gplan[o];
+  const GaussLaunched& L = Y.glaunch[o];
+  if (!L.valid) return set_err(ctx, SIFT_E_STATE, "octave not built (sift_detect_from_seed[_range])");
+  std::memset(out, 0, sizeof(*out));
+  out->kernel = L.kernel;
+  out->path = G.path;
+  out->rw = G.rw;
+  out->tile_w = G.tile_w;
+  out->tile_rows = G.tile_rows;
+  out->gx = L.gx;
+  out->gy = L.gy;
+  out->G = L.G;
+  std::copy(G.gb, G.gb + L.G + 1, out->gb);
+  out->sw = G.sw;
+  out->zero = G.zero;
+  out->keep_l64 = G.keep_l64;
+  out->vsplit = G.vsplit;
+  out->xcd_band = G.xcd_band;
+  out->vec = L.vec;
+  out->fused = L.fuse;
   return SIFT_OK;
 }
 

@@ -144,6 +144,7 @@ struct PyrState {
   std::vector<int> dims;                       // 2*O
   std::vector<double> blur, sigma;             // O*NS
   GaussPlan gplan[kMaxOctaves]{};              // of P's octaves (setup_geometry)
+  GaussLaunched glaunch[kMaxOctaves]{};        // what the last build launched for each (sift_last_gauss_plan)
   int dog_source = kNone;                      // who supplied the DoG planes
   bool have_gauss = false;                     // the Gaussian planes are materialised
   int o_first = 0;                             // first octave of the pyramid in use (sift_detect_from_seed: > 0)

@@ -4,9 +4,24 @@
 #include <algorithm>
 #include <vector>
 
+#include "../../include/sift_hip.h"
 #include "sift_gauss_dev.h"
 
 namespace sift {
+
+// sift_gauss_plan_info (include/sift_hip.h) reports these enumerators by value.
+static_assert(SIFT_GAUSS_K_STAGED8 == kKStaged8 && SIFT_GAUSS_K_STAGED16 == kKStaged16 &&
+                  SIFT_GAUSS_K_STAGED8_FUSED == kKStaged8Fused && SIFT_GAUSS_K_STAGED16_FUSED == kKStaged16Fused &&
+                  SIFT_GAUSS_K_TILES == kKTiles && SIFT_GAUSS_K_SPLIT_TILES == kKSplitTiles &&
+                  SIFT_GAUSS_K_WINDOW12 == kKWindow12 && SIFT_GAUSS_K_WINDOW16 == kKWindow16 &&
+                  SIFT_GAUSS_K_WINDOW24 == kKWindow24 && SIFT_GAUSS_K_STREAMED12 == kKStreamed12 &&
+                  SIFT_GAUSS_K_STREAMED16 == kKStreamed16 && SIFT_GAUSS_K_STREAMED24 == kKStreamed24,
+              "public kernel enumerators");
+static_assert(SIFT_GAUSS_PATH_STAGED0 == kGaussStaged0 && SIFT_GAUSS_PATH_BASE0 == kGaussBase0 &&
+                  SIFT_GAUSS_PATH_TILES == kGaussTiles && SIFT_GAUSS_PATH_SPLIT_TILES == kGaussSplitTiles &&
+                  SIFT_GAUSS_PATH_WINDOW == kGaussWindow && SIFT_GAUSS_PATH_STREAMED == kGaussStreamed &&
+                  SIFT_GAUSS_MAX_GROUPS == kMaxScales,
+              "public path enumerators");
 
 // Materialised octave-0 base (fp64), for octave-0 radii beyond kUR.
 __global__ __launch_bounds__(256) void k_upsample_base(const Pyramid P, double* __restrict__ b) {
@@ -280,7 +295,7 @@ hipError_t launch_upsample_base(const Pyramid& P, double* base0, hipStream_t st)
 }
 
 // Fills the launch fields of L from the plan and launches; decides nothing.
-hipError_t launch_gauss_dog(const Pyramid& P, const GaussPlan& G, GaussLaunch L, hipStream_t st) {
+hipError_t launch_gauss_dog(const Pyramid& P, const GaussPlan& G, GaussLaunch L, hipStream_t st, GaussLaunched* rec) {
   const Octave& oc = P.oct[L.o];
   if (L.nimg < 1) L.nimg = 1;
   if (L.fuse && (!G.can_fuse || L.nimg > 1)) return hipErrorInvalidValue;  // batches: no fused decisions
@@ -311,6 +326,7 @@ hipError_t launch_gauss_dog(const Pyramid& P, const GaussPlan& G, GaussLaunch L,
   const int k = L.fuse ? G.kernel + (kKStaged8Fused - kKStaged8) : G.kernel;
   hipLaunchKernelGGL(gauss_kernel(k), dim3(L.gx * L.gy * L.G * L.nimg), dim3(256), L.fuse ? G.lds_fused : G.lds, st, P,
                      L);
+  if (rec) *rec = GaussLaunched{true, k, L.fuse, L.gx, L.gy, L.G, L.vec};
   return hipGetLastError();
 }
 

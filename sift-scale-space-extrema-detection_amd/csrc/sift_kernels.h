@@ -243,7 +243,14 @@ struct GaussPlan {
   int gb[kMaxScales + 1];
 };
 GaussPlan gauss_plan(const Pyramid& P, int o);
-hipError_t launch_gauss_dog(const Pyramid& P, const GaussPlan& G, GaussLaunch L, hipStream_t st);
+// What launch_gauss_dog launched for an octave (sift_last_gauss_plan): the instantiation, fused variants included, and
+// the launch fields it filled.
+struct GaussLaunched {
+  bool valid;
+  int kernel, fuse, gx, gy, G, vec;
+};
+hipError_t launch_gauss_dog(const Pyramid& P, const GaussPlan& G, GaussLaunch L, hipStream_t st,
+                            GaussLaunched* rec = nullptr);
 hipError_t launch_upsample_base(const Pyramid& P, double* base0, hipStream_t st);
 // The base of octave o+1 from octave o's base alone (no planes): L_o[S] at
 // even rows / columns; vrow: seed_only_scratch(P, o) doubles.

@@ -58,7 +58,7 @@ ABI_SYMBOLS = (
     "sift_rgba_to_gray", "sift_rgba_to_gray_device", "sift_build_scale_space_rgba", "sift_detect_rgba",
     "sift_plane_image", "sift_plane_image_device", "sift_detect_begin_async", "sift_detect_end_async",
     "sift_copy_keypoint_origins_device", "sift_copy_next_seed_device", "sift_last_octave_timings",
-    "sift_last_pass_kernels",
+    "sift_last_pass_kernels", "sift_last_gauss_plan",
     "sift_detect_from_seed_range_device", "sift_merge_keypoint_blocks_device", "sift_set_owned_rows",
     "sift_last_block_counts", "sift_copy_low_contrast", "sift_set_flags",
     "sift_detect_batch_device", "sift_detect_batch_device_async", "sift_detect_batch",
@@ -144,6 +144,23 @@ class Budget(ctypes.Structure):
 
 BUDGET_MAX_CELLS = 16384
 
+# sift_gauss_plan_info.kernel / .path (include/sift_hip.h)
+(GAUSS_K_STAGED8, GAUSS_K_STAGED16, GAUSS_K_STAGED8_FUSED, GAUSS_K_STAGED16_FUSED, GAUSS_K_TILES, GAUSS_K_SPLIT_TILES,
+ GAUSS_K_WINDOW12, GAUSS_K_WINDOW16, GAUSS_K_WINDOW24, GAUSS_K_STREAMED12, GAUSS_K_STREAMED16,
+ GAUSS_K_STREAMED24) = range(12)
+(GAUSS_PATH_STAGED0, GAUSS_PATH_BASE0, GAUSS_PATH_TILES, GAUSS_PATH_SPLIT_TILES, GAUSS_PATH_WINDOW,
+ GAUSS_PATH_STREAMED) = range(6)
+GAUSS_MAX_GROUPS = 12
+
+
+class GaussPlanInfo(ctypes.Structure):
+    _fields_ = [("kernel", ctypes.c_int32), ("path", ctypes.c_int32), ("rw", ctypes.c_int32),
+                ("tile_w", ctypes.c_int32), ("tile_rows", ctypes.c_int32), ("gx", ctypes.c_int32),
+                ("gy", ctypes.c_int32), ("G", ctypes.c_int32), ("gb", ctypes.c_int32 * (GAUSS_MAX_GROUPS + 1)),
+                ("sw", ctypes.c_int32), ("zero", ctypes.c_int32), ("keep_l64", ctypes.c_int32),
+                ("vsplit", ctypes.c_int32), ("xcd_band", ctypes.c_int32), ("vec", ctypes.c_int32),
+                ("fused", ctypes.c_int32)]
+
 
 def make_budget(max_total=None, cell_px=0, max_per_cell=None):
     """sift_budget: None = no limit (stored as -1); cell_px 0 = no grid."""
@@ -216,6 +233,7 @@ def lib():
         "sift_last_timings": (ctypes.c_int, [vp, ctypes.POINTER(Timings)]),
         "sift_last_octave_timings": (ctypes.c_int, [vp, dp, ctypes.c_int, ip]),
         "sift_last_pass_kernels": (ctypes.c_int, [vp, ctypes.c_char_p, sz, szp]),
+        "sift_last_gauss_plan": (ctypes.c_int, [vp, ctypes.c_int, ctypes.POINTER(GaussPlanInfo)]),
         "sift_detect_from_seed_range_device": (ctypes.c_int, [vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int,
                                                               ctypes.c_int, pp, vp, sz, szp]),
         "sift_merge_keypoint_blocks_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(ctypes.c_int64), ctypes.c_int,
@@ -785,6 +803,16 @@ class Context:
         buf = ctypes.create_string_buffer(n.value + 1)
         self._check(self._L.sift_last_pass_kernels(self._h, buf, n.value + 1, ctypes.byref(n)), "sift_last_pass_kernels")
         return buf.value.decode()
+
+    def gauss_plan(self, octave):
+        """The launch plan of one octave's Gaussian+DoG pass as the last build
+        / detection launched it (sift_last_gauss_plan): a dict of the record's
+        fields, gb cut to its G + 1 boundaries."""
+        g = GaussPlanInfo()
+        self._check(self._L.sift_last_gauss_plan(self._h, int(octave), ctypes.byref(g)), "sift_last_gauss_plan")
+        d = {name: int(getattr(g, name)) for name, _ in GaussPlanInfo._fields_ if name != "gb"}
+        d["gb"] = [int(v) for v in g.gb[:g.G + 1]]
+        return d
 
     # -- orientation assignment and descriptors ------------------------------
     def orient(self):
