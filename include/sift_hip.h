@@ -1025,6 +1025,110 @@ int sift_copy_keypoint_selection(struct sift_ctx *ctx, int32_t *index, size_t ca
  * read-back and the emission. */
 int sift_last_select_timing(struct sift_ctx *ctx, double *select_ms);
 
+/* ---- Guided descriptor matching ---------------------------------------------------
+ *
+ * The descriptor match restricted by a homography: for every query row, the
+ * nearest and second-nearest descriptor among the train rows whose position lies
+ * within `radius` input pixels of the projection H x of the query row's position.
+ * The result is a lexicographic minimum of integer keys over a set that the
+ * rules below fix, so it is exact, does not depend on the grid or on how the work
+ * is split, and is bit-identical from run to run.  It is written as struct
+ * sift_match records: sift_match_select, sift_pair_points_device, the RANSAC and
+ * the refit follow unchanged.  These entry points are detected by symbol;
+ * SIFT_ABI_VERSION stayed 10.
+ *
+ * Inputs: query and train rows of SIFT_DESC_BYTES uint8 (16-byte aligned in
+ * device memory), optional byte masks as in sift_match, one sift_point per row,
+ * h[9] row-major mapping query positions to train positions (as the RANSAC's;
+ * not validated), radius (finite, > 0, input pixels), and train_width,
+ * train_height > 0, which only shape the grid: train points outside the image
+ * take part like any other.  All arithmetic is fp64 without contraction, + - * /,
+ * comparisons and floor alone.
+ *
+ * Projection of query row q at (x, y), by the warp's rule:
+ *   u = (h0*x + h1*y) + h2, v = (h3*x + h4*y) + h5, w = (h6*x + h7*y) + h8,
+ *   rinv = 1.0 / w, px = u * rinv, py = v * rinv.
+ * The row is PROJECTED iff it is unmasked, w > 0, and px and py are finite
+ * (px - px == 0.0 and py - py == 0.0); a NaN anywhere compares false.
+ *
+ * Candidates, with r2 = radius * radius formed once on the host: train row t at
+ * (tx, ty) is a candidate of a projected row q iff t is unmasked and
+ *   (dx*dx + dy*dy) <= r2,  dx = tx - px, dy = ty - py
+ * (each product rounded, then added).  A NaN train coordinate never passes.
+ *
+ * Result, per query row: the two smallest (d2, t) over its candidates in
+ * lexicographic order, d2 the integer squared distance of sift_match: the lowest
+ * train index wins among equal distances, and `second` may be at the distance of
+ * `best`.  A missing neighbour is (-1, SIFT_MATCH_NONE_D2) exactly as in
+ * sift_match: both for a masked or unprojected row and for a row without a
+ * candidate, `second` alone for a row with exactly one.
+ *
+ * Grid.  It is internal and changes no record; it is stated because n_visited
+ * below is defined by it.  cell_px is the smallest integer
+ *   c >= max(1, min(ceil(radius), max(train_width, train_height)))
+ * with ceil(W / c) * ceil(H / c) <= SIFT_GUIDED_MAX_CELLS; ncx = ceil(W / c), ncy =
+ * ceil(H / c).  The column of a coordinate a is the budget's clamped rule:
+ *   t = a / (double)c;  col(a) = t >= 0 ? (t < ncx ? (int)floor(t) : ncx - 1) : 0
+ * (the test comes before the cast); rows likewise with ncy.  An unmasked train
+ * row with two non-NaN coordinates is filed in cell (row(ty), col(tx)).  A
+ * projected query row VISITS the train rows filed in columns
+ * col(px - radius) - 1 .. col(px + radius) + 1 and rows row(py - radius) - 1 ..
+ * row(py + radius) + 1, both clamped to the grid.  The margin of one cell is
+ * there because the rounded distance test can admit a point a few ulp beyond
+ * radius and col is only monotone; DESIGN.md section 18 proves that every
+ * candidate is visited, for huge and overflowing coordinates and radii too.
+ *
+ * Limits: counts below 2^31 - 1; pointers non-NULL where a count is non-zero, h
+ * non-NULL; device descriptors 16-byte aligned; radius finite and > 0;
+ * train_width > 0 and train_height > 0: else SIFT_E_ARG with nothing written.
+ * n_query == 0 and n_train == 0 are valid (no train rows: every neighbour
+ * missing).
+ *
+ * Not here: gates on scale or orientation, a fundamental-matrix or epipolar band,
+ * a symmetric both-ways call, batches.  A mutual check is done the existing way:
+ * run the guided match again with the two sets swapped and the matrix of
+ * sift_homography_inverse, and pass its records as d_rev to sift_match_select. */
+typedef struct {
+  double x, y;
+} sift_point; /* 16 bytes */
+#define SIFT_GUIDED_MAX_CELLS (1 << 20)
+typedef struct {
+  int32_t cell_px, ncx, ncy, reserved; /* the grid; reserved is 0 */
+  int64_t n_projected;                 /* projected query rows */
+  int64_t n_visited;                   /* sum over projected rows of visited train rows */
+  int64_t n_candidates;                /* sum over projected rows of candidates */
+} sift_guided_info;                    /* 40 bytes */
+
+/* Everything in device memory of ctx's device but h; d_out for n_query records.
+ * Ordered on ctx's stream, complete on return.  Writes d_out alone: the context's
+ * last match (sift_device_matches) stays what it was. */
+int sift_match_guided_device(struct sift_ctx *ctx, const uint8_t *d_query, const uint8_t *d_query_mask,
+                             const sift_point *d_query_xy, size_t n_query, const uint8_t *d_train,
+                             const uint8_t *d_train_mask, const sift_point *d_train_xy, size_t n_train, int train_width,
+                             int train_height, const double h[9], double radius, struct sift_match *d_out);
+/* The same with host arrays, through the context's own device buffers; the
+ * records become the context's last match, as sift_match's. */
+int sift_match_guided(struct sift_ctx *ctx, const uint8_t *query, const uint8_t *query_mask, const sift_point *query_xy,
+                      size_t n_query, const uint8_t *train, const uint8_t *train_mask, const sift_point *train_xy,
+                      size_t n_train, int train_width, int train_height, const double h[9], double radius,
+                      struct sift_match *out);
+
+/* Query = the last sift_describe of ctx, train = that of train_ctx on the same
+ * device, rows and masks exactly as sift_match_features; a row's position is
+ * abs_x, abs_y of the keypoint its orientation record names (the gather of
+ * sift_pair_points_device), and the train size is train_ctx's input size.  The
+ * records become ctx's last match and stay on the device when out == NULL.
+ * SIFT_E_STATE without a describe on either side, SIFT_E_ARG across devices,
+ * SIFT_E_CAPACITY as sift_match_features. */
+int sift_match_features_guided(struct sift_ctx *ctx, struct sift_ctx *train_ctx, const double h[9], double radius,
+                               struct sift_match *out, size_t cap, size_t *n_out);
+
+/* The grid and the three sums of the last guided match on ctx through any form
+ * (SIFT_E_STATE without one), and its device time in milliseconds: the filing
+ * (cells, scan, fill) and the match. */
+int sift_last_guided_info(struct sift_ctx *ctx, sift_guided_info *out);
+int sift_last_guided_timings(struct sift_ctx *ctx, double *grid_ms, double *match_ms);
+
 /* Wait for all work queued on ctx's stream. */
 int sift_synchronize(struct sift_ctx *ctx);
 

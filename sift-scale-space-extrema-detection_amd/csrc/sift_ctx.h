@@ -1,6 +1,6 @@
 // The context behind the C ABI, its state grouped by stage, and what its host files share: sift_api.hip (lifetime,
 // shared helpers), sift_api_pyramid / _extrema / _detect / _shard / _image.hip (detection) and sift_api_feature /
-// _match / _verify / _refit / _warp / _budget.hip (later stages).  No kernel file includes this.
+// _match / _verify / _refit / _warp / _budget / _guided.hip (later stages).  No kernel file includes this.
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -127,6 +127,19 @@ struct BudgetState {
   bool have_sel = false;                       // ... while its list is the context's list
   EventSet<2> ev;                              // around one selection
   double select_ms = 0;
+};
+
+// Guided descriptor matching (sift_api_guided.hip); the host and features forms leave their records in MatchState::out.
+struct GuidedState {
+  DBuf cell, count, off;                       // per train row: its cell; per cell (+ 1): rows, their exclusive scan
+  DBuf fxy, ftag, frows;                       // the train rows filed in cell order (GuidedFiled)
+  DBuf info;                                   // three 64-bit sums of the last match
+  DBuf in_q, in_t, in_qm, in_tm, in_qxy, in_txy;  // host-form inputs; the features form gathers into in_qxy / in_txy
+  HBuf hinfo;                                  // pinned read-back of info
+  sift_guided_info last{};                     // of the last guided match,
+  bool have = false;                           // ... when there was one
+  EventSet<3> ev;                              // before the filing [0], between it and the match [1], after it [2]
+  double grid_ms = 0, match_ms = 0;
 };
 
 // Taps of the deepest schedule built so far (setup_geometry): per-(octave, scale) sigma, the padded tap vector, its
@@ -318,6 +331,7 @@ struct sift_ctx {
   sift::RefitState refit;
   sift::WarpState warp;
   sift::BudgetState budget;
+  sift::GuidedState guided;
   HBuf hscratch;                  // pinned: one sift::StageScratch (sift_ctx_create)
   DBuf counters, temp;             // kCntAll counter slots (sift_kernels.h); scan scratch
   HBuf h_counters;                 // pinned mirror of counters

@@ -539,6 +539,43 @@ hipError_t launch_budget_fill(unsigned* flag, int n, hipStream_t st);
 hipError_t launch_budget_emit(const unsigned* flag, const unsigned* off, int n, unsigned cap, int32_t* index,
                               const Keypoint* kp, Keypoint* kp_out, hipStream_t st);
 
+// Guided descriptor matching (sift_guided.hip; the definition is in include/sift_hip.h).
+constexpr int kGuidedMaxCells = 1 << 20;
+constexpr int kGuidedMatchBlocks = 8192;  // one-wave blocks of one match launch: 32 waves on each of 256 CUs
+struct GuidedGrid {
+  int cell_px, ncx, ncy;
+};
+// The grid of the definition for a train size and a radius (both validated).
+GuidedGrid guided_grid(int width, int height, double radius);
+// The train rows in cell order: slot j holds a row's position, (index, squared norm) and 128 bytes.
+struct GuidedFiled {
+  double2* xy;
+  int2* tag;
+  unsigned char* rows;
+};
+struct GuidedMatch {
+  const unsigned char* query;   // n_query x 128, 16-byte aligned
+  const unsigned char* qmask;   // or nullptr
+  const double2* qxy;
+  int n_query;
+  double h[9], radius, r2;
+  GuidedGrid grid;
+  const unsigned* off;          // cells + 1: the exclusive scan of the cell counts
+  GuidedFiled filed;
+  Match* out;
+  unsigned long long* info;     // projected rows, visited rows, candidates: added to (zeroed by the caller)
+};
+// xy[r] = (abs_x, abs_y) of the keypoint record r names; NaNs when the index is outside the list.
+hipError_t launch_guided_gather(const Orientation* ori, int n, const Keypoint* kp, int n_kp, double2* xy,
+                                hipStream_t st);
+// cell[i] of the n train rows (-1: masked or a NaN coordinate); count[c] += 1 (cells + 1 zeroed words).
+hipError_t launch_guided_cells(const double2* xy, const unsigned char* mask, int n, const GuidedGrid& g, int* cell,
+                               unsigned* count, hipStream_t st);
+// Files the rows with cell[i] >= 0: off = the exclusive scan of count, which is counted back down to zero.
+hipError_t launch_guided_fill(const unsigned char* rows, const double2* xy, const int* cell, int n, const unsigned* off,
+                              unsigned* count, const GuidedFiled& F, hipStream_t st);
+hipError_t launch_guided_match(const GuidedMatch& M, hipStream_t st);
+
 // Image products either side of the path (sift_image.hip).
 // gray/alpha rows are dense (w floats); alpha may be nullptr.
 hipError_t launch_rgba_to_gray(const unsigned char* rgba, size_t stride_bytes, int w, int h, float* gray,

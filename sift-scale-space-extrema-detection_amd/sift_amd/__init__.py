@@ -76,6 +76,8 @@ ABI_SYMBOLS = (
     "sift_last_warp_timing",
     "sift_keypoint_select_device", "sift_keypoint_select", "sift_limit_keypoints", "sift_copy_keypoint_selection",
     "sift_last_select_timing",
+    "sift_match_guided_device", "sift_match_guided", "sift_match_features_guided", "sift_last_guided_info",
+    "sift_last_guided_timings",
 )
 
 
@@ -143,6 +145,15 @@ class Budget(ctypes.Structure):
 
 
 BUDGET_MAX_CELLS = 16384
+
+POINT_DTYPE = np.dtype([("x", "<f8"), ("y", "<f8")])
+GUIDED_MAX_CELLS = 1 << 20
+
+
+class GuidedInfo(ctypes.Structure):
+    _fields_ = [("cell_px", ctypes.c_int32), ("ncx", ctypes.c_int32), ("ncy", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("n_projected", ctypes.c_int64), ("n_visited", ctypes.c_int64),
+                ("n_candidates", ctypes.c_int64)]
 
 # sift_gauss_plan_info.kernel / .path (include/sift_hip.h)
 (GAUSS_K_STAGED8, GAUSS_K_STAGED16, GAUSS_K_STAGED8_FUSED, GAUSS_K_STAGED16_FUSED, GAUSS_K_TILES, GAUSS_K_SPLIT_TILES,
@@ -308,6 +319,13 @@ def lib():
         "sift_limit_keypoints": (ctypes.c_int, [vp, bp, szp]),
         "sift_copy_keypoint_selection": (ctypes.c_int, [vp, vp, sz, szp]),
         "sift_last_select_timing": (ctypes.c_int, [vp, dp]),
+        "sift_match_guided_device": (ctypes.c_int, [vp, vp, vp, vp, sz, vp, vp, vp, sz, ctypes.c_int, ctypes.c_int, dp,
+                                                    ctypes.c_double, vp]),
+        "sift_match_guided": (ctypes.c_int, [vp, vp, vp, vp, sz, vp, vp, vp, sz, ctypes.c_int, ctypes.c_int, dp,
+                                             ctypes.c_double, vp]),
+        "sift_match_features_guided": (ctypes.c_int, [vp, vp, dp, ctypes.c_double, vp, sz, szp]),
+        "sift_last_guided_info": (ctypes.c_int, [vp, ctypes.POINTER(GuidedInfo)]),
+        "sift_last_guided_timings": (ctypes.c_int, [vp, dp, dp]),
     }
     for name, (res, args) in sig.items():
         f = getattr(L, name)
@@ -932,6 +950,71 @@ class Context:
         self._check(self._L.sift_last_match_timings(self._h, ctypes.byref(a), ctypes.byref(b)),
                     "sift_last_match_timings")
         return dict(match_ms=a.value, select_ms=b.value)
+
+    # -- guided descriptor matching --------------------------------------------
+    @staticmethod
+    def _xy(xy, n):
+        """Positions as POINT_DTYPE [n], from that dtype or from an [n, 2] array."""
+        a = np.asarray(xy)
+        if a.dtype != POINT_DTYPE:
+            a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2).view(POINT_DTYPE).reshape(-1)
+        a = np.ascontiguousarray(a)
+        if a.shape != (n,):
+            raise ValueError("one position per row")
+        return a
+
+    @staticmethod
+    def _h9(h):
+        h = np.ascontiguousarray(h, dtype=np.float64).reshape(-1)
+        if h.shape != (9,):
+            raise ValueError("h must have nine entries")
+        return h
+
+    def match_guided(self, query, query_xy, train, train_xy, train_size, h, radius, query_mask=None,
+                     train_mask=None):
+        """The two nearest train rows of every query row among those within
+        `radius` pixels of h applied to the query row's position
+        (sift_match_guided): MATCH_DTYPE [n_query].  train_size = (width,
+        height); positions are [n, 2] arrays or POINT_DTYPE."""
+        q, t = self._rows(query), self._rows(train)
+        qm, tm = self._mask(query_mask, q.shape[0]), self._mask(train_mask, t.shape[0])
+        qxy, txy = self._xy(query_xy, q.shape[0]), self._xy(train_xy, t.shape[0])
+        h = self._h9(h)
+        out = np.zeros(q.shape[0], dtype=MATCH_DTYPE)
+        self._check(self._L.sift_match_guided(self._h, self._ptr(q), self._ptr(qm), self._ptr(qxy), q.shape[0],
+                                              self._ptr(t), self._ptr(tm), self._ptr(txy), t.shape[0],
+                                              int(train_size[0]), int(train_size[1]),
+                                              h.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), float(radius),
+                                              self._ptr(out)), "sift_match_guided")
+        return out
+
+    def match_features_guided(self, train_ctx, h, radius):
+        """This context's last describe() against train_ctx's within `radius` of
+        h x, on the device (sift_match_features_guided): MATCH_DTYPE [records
+        of this context]."""
+        n = ctypes.c_size_t()
+        self._L.sift_device_features(self._h, None, None, None, ctypes.byref(n))  # the record count; 0 without features
+        out = np.zeros(max(n.value, 1), dtype=MATCH_DTYPE)
+        h = self._h9(h)
+        self._check(self._L.sift_match_features_guided(self._h, train_ctx._h,
+                                                       h.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                       float(radius), out.ctypes.data_as(ctypes.c_void_p),
+                                                       out.shape[0], ctypes.byref(n)), "sift_match_features_guided")
+        return out[:n.value]
+
+    def guided_info(self):
+        """The grid and the three sums of the last guided match (sift_last_guided_info)."""
+        g = GuidedInfo()
+        self._check(self._L.sift_last_guided_info(self._h, ctypes.byref(g)), "sift_last_guided_info")
+        return dict(cell_px=g.cell_px, ncx=g.ncx, ncy=g.ncy, n_projected=g.n_projected, n_visited=g.n_visited,
+                    n_candidates=g.n_candidates)
+
+    def guided_timings(self):
+        """Device ms of the last guided match: the filing of the train rows, and the match."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        self._check(self._L.sift_last_guided_timings(self._h, ctypes.byref(a), ctypes.byref(b)),
+                    "sift_last_guided_timings")
+        return dict(grid_ms=a.value, match_ms=b.value)
 
     # -- RANSAC homography verification ---------------------------------------
     @staticmethod
