@@ -467,8 +467,15 @@ int sift_detect_rgba(struct sift_ctx *ctx, const uint8_t *rgba, int width, int h
  *                         matrix2d.js:151; DoG chunks use 5, background.js:303)
  *   SIFT_DISPLAY_SAMPLED  (v-min)/(max-min) over the plane (Matrix2D_sampledNormalize,
  *                         matrix2d.js:169; DoG images, background.js:336, :387)
- * computed in fp64 from the fp32 plane.  `rgba` holds rows*cols*4 bytes
- * (cap_bytes); host memory, or device memory in the _device form. */
+ * computed in fp64 from the fp32 plane.  The sampled mode's min and max are
+ * the reference's scan: it starts at min = Number.MAX_SAFE_INTEGER = 2^53 - 1
+ * and max = Number.MIN_SAFE_INTEGER = -(2^53 - 1) and moves them with strict
+ * `value < min` / `value > max`, so NaNs never win, a plane with no value
+ * below 2^53 - 1 keeps that minimum and one with none above -(2^53 - 1) that
+ * maximum (a constant plane of 1e30 is white, not 0 / 0).  The plain and
+ * sampled bytes equal the reference's for any plane, these included.  `rgba`
+ * holds rows*cols*4 bytes (cap_bytes); host memory, or device memory in the
+ * _device form (4-byte aligned; 16-byte aligned takes 16-byte stores). */
 enum { SIFT_DISPLAY_PLAIN = 0, SIFT_DISPLAY_SIGMOID = 1, SIFT_DISPLAY_SAMPLED = 2 };
 int sift_plane_image(struct sift_ctx *ctx, int kind, int octave, int scale, int mode, double coefficient,
                      uint8_t *rgba, size_t cap_bytes);

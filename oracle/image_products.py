@@ -7,6 +7,8 @@ tests/golden/image_products.npz, produced by the reference's own functions
 """
 import numpy as np
 
+MAX_SAFE_INTEGER = float(2 ** 53 - 1)  # Number.MAX_SAFE_INTEGER; Number.MIN_SAFE_INTEGER is its negative
+
 
 def rgba_to_gray(rgba):
     """ImageUtils_convertImageDataToMatrix2D({convertToGrayscale: true,
@@ -33,18 +35,22 @@ def to_uint8_clamped(p):
 def sigmoid_normalize(m, coefficient=1.0):
     """Matrix2D_sigmoidNormalize (matrix2d.js:151-158)."""
     x = np.asarray(m, dtype=np.float64)
-    with np.errstate(over="ignore"):
+    with np.errstate(over="ignore", invalid="ignore"):
         return 1.0 / (1.0 + np.exp(coefficient * (-1.0 * x)))
 
 
 def sampled_normalize(m):
-    """Matrix2D_sampledNormalize (matrix2d.js:169-193): min/max scan with
-    `value < min` / `value > max` (NaNs never win), then (v-min)/(max-min)."""
+    """Matrix2D_sampledNormalize (matrix2d.js:169-193): the min/max scan
+    starts at min = Number.MAX_SAFE_INTEGER = 2^53 - 1 and max =
+    Number.MIN_SAFE_INTEGER = -(2^53 - 1) and moves them with strict
+    `value < min` / `value > max` (NaNs never win), then (v-min)/(max-min).
+    A plane with no value below 2^53 - 1 keeps the start minimum, one with
+    none above -(2^53 - 1) the start maximum."""
     x = np.asarray(m, dtype=np.float64)
-    finite = x[~np.isnan(x)]
-    mn = finite.min() if finite.size else float(2 ** 53 - 1)
-    mx = finite.max() if finite.size else -float(2 ** 53 - 1)
-    with np.errstate(invalid="ignore", divide="ignore"):
+    seen = x[~np.isnan(x)]
+    mn = min(seen.min(), MAX_SAFE_INTEGER) if seen.size else MAX_SAFE_INTEGER
+    mx = max(seen.max(), -MAX_SAFE_INTEGER) if seen.size else -MAX_SAFE_INTEGER
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         return (x - mn) / (mx - mn)
 
 

@@ -20,7 +20,13 @@
 //   All in fp64 from the fp32 plane values.  The plane min/max of the
 //   sampled mode is a two-level reduction: k_minmax_partial writes one
 //   (min, max) per block, every block of k_plane_image folds the partials
-//   (<= 1024 pairs, L2-resident) before its pixels.
+//   (<= 1024 pairs, L2-resident) before its pixels.  The reference's scan
+//   starts at min = Number.MAX_SAFE_INTEGER = 2^53 - 1 and max =
+//   Number.MIN_SAFE_INTEGER = -(2^53 - 1) and moves them with strict
+//   `value < min` / `value > max` (matrix2d.js:174-186): the fp32 partials
+//   start at +-inf, and the fold clamps them to those two values in fp64,
+//   so a plane with no value at or below 2^53 - 1 keeps the start minimum
+//   (likewise the maximum), as the reference does.
 #include "sift_kernels.h"
 
 #pragma clang fp contract(off)
@@ -161,8 +167,10 @@ __global__ void __launch_bounds__(256) k_plane_image(const float* __restrict__ v
       }
     }
     __syncthreads();
-    mn = (double)s_mn;
-    range = (double)s_mx - mn;  // matrix2d.js:192: (v - min) / (max - min)
+    // The reference's scan starts at Number.MAX_SAFE_INTEGER / MIN_SAFE_INTEGER (matrix2d.js:174-175): a plane
+    // wholly above 2^53 - 1 keeps that minimum, one wholly below -(2^53 - 1) that maximum.
+    mn = fmin((double)s_mn, 9007199254740991.0);
+    range = fmax((double)s_mx, -9007199254740991.0) - mn;  // matrix2d.js:191: (v - min) / (max - min)
   }
   const long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long x0 = q * 4;
